@@ -25,7 +25,13 @@ the global batch of one step is fixed and dealt over the ranks (192 / N batches 
 figure (192 batches per rank) is reported beside it as "weak".  Barrier + synchronize bracket the timed
 region and the time is the max over ranks.
 
-Run:  python bench.py [--gpus N --steps K --warmup W --config {1,2,4}]
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure, the
+kernel table and roofline read from the timed steps themselves).  --full adds every leg that takes runs of
+its own: the CPU baseline, the k-hop-alone, drop-in, aux and 3-in-flight legs, the edge tables' build time
+and, with several ranks, the other scaling mode.  --dump-outputs DIR writes the last timed step's outputs
+as DIR/<name>.npy (same arguments = same inputs, so two builds can be compared output for output).
+
+Run:  python bench.py [--gpus N --steps K --warmup W --config {1,2,4} --full --dump-outputs DIR]
 """
 import argparse
 import json
@@ -340,7 +346,8 @@ def cpu_baseline(g, rows, events, pool, N, M, B, seed, sd, budget_s=4.0, max_bat
 
 # ----------------------------------------------------------------------------------------------- timing
 def timed(run_step, pipes, inputs, warmup, steps, dist, backend, dev, L):
-    """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; max over ranks."""
+    """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; max over ranks.
+    Also returns what run_step returned for the last timed step."""
     from tempme_amd.sharding import max_over_ranks
     for k in range(warmup):
         run_step(inputs[k % len(inputs)])
@@ -351,9 +358,10 @@ def timed(run_step, pipes, inputs, warmup, steps, dist, backend, dev, L):
         dist.barrier()
     torch.cuda.synchronize()
     L.profile_enable(True)
+    last = None
     t0 = time.perf_counter()
     for k in range(warmup, warmup + steps):
-        run_step(inputs[k % len(inputs)])
+        last = run_step(inputs[k % len(inputs)])
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -362,7 +370,33 @@ def timed(run_step, pipes, inputs, warmup, steps, dist, backend, dev, L):
     L.profile_enable(False)
     for p in pipes:
         p.check_errors()
-    return max_over_ranks(el, dist, dev if backend == "nccl" else "cpu"), prof
+    return max_over_ranks(el, dist, dev if backend == "nccl" else "cpu"), prof, last
+
+
+DUMP_BUDGET_BYTES = 48 << 20       # all dumped arrays together (float32), under the 64 MB a dump may take
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(outputs, out_dir, rank, world):
+    """Write the last timed step's outputs (name -> device tensor) as ``out_dir/<name>.npy`` (float32; one rank's
+    shard per file, ``<name>_rank<r>.npy`` with several ranks).  The arrays share DUMP_BUDGET_BYTES, smallest
+    first; one that does not fit is written as a fixed, seeded sample of its rows (all leading dimensions
+    flattened, ascending row order), the same rows in every run of the same shapes.  Several ranks split the
+    budget evenly."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES // world
+    names = sorted(outputs, key=lambda n: outputs[n].numel())
+    for i, name in enumerate(names):
+        t = outputs[name].detach()
+        share = left // (len(names) - i)
+        if t.numel() * 4 > share:
+            t = t.reshape(-1, t.shape[-1])
+            keep = max(1, share // (4 * t.shape[1]))
+            rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
 
 
 @torch.no_grad()
@@ -431,8 +465,16 @@ def main():
     ap.add_argument("--n-degree", type=int, default=None)
     ap.add_argument("--alpha", type=float, default=1.2)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the k-hop-alone, drop-in and aux legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the CPU baseline, the k-hop-alone, drop-in, "
+                         "aux and 3-in-flight legs, the edge tables' build time and, with several ranks, the other "
+                         "scaling mode.  Without it only the headline figure is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (imp, hop-1 and hop-2 weights, the contrast scores "
+                         "when one runs) as DIR/<name>.npy, float32; a large array as a fixed seeded sample of its rows")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the k-hop-alone, drop-in, aux and 3-in-flight legs")
     ap.add_argument("--weak", action="store_true", help="primary line weak scaling (--batches per rank)")
     ap.add_argument("--no-edge-table", action="store_true",
                     help="lin_event's edge-feature product per walk position instead of per edge id")
@@ -539,9 +581,11 @@ def main():
         pipes = [pipe]
 
         def run_step(x):
-            _, h1, _ = pipe.run(*x)
+            imp, h1, h2 = pipe.run(*x)
+            res = {"imp": imp, "h1": h1, "h2": h2}
             if gm is not None:
-                gm_contrast(gm, pipe.buf, x, h1)
+                res["contrast"] = gm_contrast(gm, pipe.buf, x, h1)
+            return res
     else:
         flight = PipelinedExplainer(ex, finder.graph, torch.from_numpy(pool), N, M, B, seed=args.seed, depth=S,
                                     edge_table=not args.no_edge_table, chain_encoders=not overlap)
@@ -549,7 +593,8 @@ def main():
         pipe = pipes[0]
 
         def run_step(x):
-            flight.submit(*x)
+            (imp, h1, h2), _ = flight.submit(*x)
+            return {"imp": imp, "h1": h1, "h2": h2}
 
     n_steps = args.warmup + args.steps
     strong = not args.weak
@@ -568,25 +613,29 @@ def main():
     for k in range(S):                             # every stream's buffers allocated before timing
         run_step(inputs[k % n_steps])
     builds0 = pipe.tabs.builds
-    el, prof = timed(run_step, pipes, inputs, args.warmup, args.steps, dist, backend, dev, L)
+    el, prof, last = timed(run_step, pipes, inputs, args.warmup, args.steps, dist, backend, dev, L)
     tab_builds = pipe.tabs.builds - builds0
+    if args.dump_outputs and last is not None:     # before any other leg reuses the pipelines' buffers
+        dump_outputs(last, args.dump_outputs, rank, world)
+    del last
+    extras = args.full and not args.no_extras
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         # the secondary figure: the other scaling mode on the same ranks
         per_rank2 = (args.batches if strong else args.batches // world) * B
         inputs2 = make_inputs(n_steps, rank, world, per_rank2, (src, dst, ts, eidx), dev)
         run_step(inputs2[0])
-        el2, _ = timed(run_step, pipes, inputs2, args.warmup, args.steps, dist, backend, dev, L)
+        el2, _, _ = timed(run_step, pipes, inputs2, args.warmup, args.steps, dist, backend, dev, L)
         weak = {"scaling": "weak" if strong else "strong", "value": round(world * args.steps * per_rank2 / el2, 2),
                 "ms_per_step": round(el2 / args.steps * 1e3, 3), "events_per_step_per_gpu": per_rank2}
     pipelined = None
-    if world == 1 and S == 1 and not args.no_extras and gm is None:
+    if world == 1 and S == 1 and extras and gm is None:
         # like-for-like with the multi-rank lines: the same step with 3 steps in flight and overlapping walk kernels
         fl3 = PipelinedExplainer(ex, finder.graph, torch.from_numpy(pool), N, M, B, seed=args.seed, depth=3,
                                  edge_table=not args.no_edge_table, chain_encoders=False)
         for k in range(3):
             fl3.submit(*inputs[k % n_steps])
-        el3, _ = timed(lambda x: fl3.submit(*x), fl3.pipes, inputs, args.warmup, args.steps, dist, backend, dev, L)
+        el3, _, _ = timed(lambda x: fl3.submit(*x), fl3.pipes, inputs, args.warmup, args.steps, dist, backend, dev, L)
         pipelined = {"value": round(args.steps * per_rank / el3, 2), "ms_per_step": round(el3 / args.steps * 1e3, 3),
                      "steps_in_flight": 3, "walk_overlap": True,
                      "what": "the same timed steps with 3 steps in flight, consecutive walk kernels overlapping (the "
@@ -635,9 +684,10 @@ def main():
         if samp and traffic.get("events_kernel") is not None:
             samp["traffic"] = traffic["events_kernel"]
         # the per-edge-id tables (gate factor + lin_event's edge product over all edge ids) are a function of the
-        # weight state, the edge-feature table and the graph: built once (EdgeTables), timed here alone
-        pipe.tabs.build(timed=True)
-        edge_tables = {"ms": round(pipe.tabs.build_ms, 3), "edge_ids": int(pipe.gf.numel()),
+        # weight state, the edge-feature table and the graph: built once (EdgeTables), timed alone under --full
+        if args.full:
+            pipe.tabs.build(timed=True)
+        edge_tables = {"ms": round(pipe.tabs.build_ms, 3) if args.full else None, "edge_ids": int(pipe.gf.numel()),
                        "builds_in_timed_region": tab_builds,
                        "what": "tm_edge_tables (gate_reg_kernel) over every edge id: built once per weight state "
                                "(tm_weights_version), edge-feature table and graph, outside the per-step unit; the "
@@ -646,7 +696,7 @@ def main():
         out = {"metric": METRIC, "value": round(total / el, 2), "unit": "edges/s", "n_gpus": n_gpus, "ranks": world,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(el / args.steps * 1e3, 3),
                "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None,
-               "dtype": "fp32",
+               "dtype": "fp32", "full": args.full,
                "data": "synthetic (seeded graph of the config's shape, random-init TempME weights)",
                "config": {"workload": workload, "config": f"configs[{args.config}]" if args.config != 2 else
                           "metric (full Enron + TGN, n_degree=20)", "n_degree": N, "walks_per_slot": M,
@@ -660,11 +710,11 @@ def main():
             out["weak" if strong else "strong"] = weak
         if pipelined is not None:
             out["pipelined"] = pipelined
-        if not args.no_extras:
+        if extras:
             out["khop_roofline"] = khop_alone(pipe, inputs, min(args.steps, 5), N, group=8)
             out["dropin"] = dropin_leg(ex, pipe, inputs, B, N)
             out["aux"] = aux_rows(finder, src, dst, ts, eidx, pool, graph_build_ms)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             sd = {k: v.detach().cpu() for k, v in ex.state_dict().items()}
             gm_sd = None if gm is None else {k: v.detach().cpu() for k, v in gm.state_dict().items()}
             out["cpu_baseline"] = cpu_baseline(g, rows, (src, dst, ts, eidx), pool, N, M, B, args.seed, sd, gm_sd=gm_sd)

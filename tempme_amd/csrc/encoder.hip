@@ -1271,13 +1271,17 @@ struct Stash {
 
 // Attention head + final MLP for the 16 walks of this wave (explainer_new.py:789-846 and :121-125,
 // :195-201) in the folded form: score_i = V . H_i + cw, alpha = softmax(score * time weight),
-// hid = relu(P2 + alpha_0 R_0 + alpha_1 R_1) (R_i = A1G H_i; alpha_0 + alpha_1 = 1 carries a1 beta),
+// hid = relu(P2 + A1G (alpha_0 H_0 + alpha_1 H_1)) (alpha_0 + alpha_1 = 1 carries a1 beta),
 // M1 = relu(M1A2 hid + tc[cat]), M2 = relu(m2 M1 + b), imp = sigmoid(m3 . M2 + b).
-template <int NQE, int NTD>
+// A1G is linear, so it is applied once per walk, to the mixed hidden vector, not once per position
+// (H0, H1 = the two positions' H, U in the zero-node form; `pre` holds A1G's first fragments on entry);
+// P2 is the accumulators' initial value.
+template <int NQE, int NTD, bool ZN, int NA>
 __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs, int64_t gw,
                                           bool valid, const HeadIn &hi, const Stash &st, float s0, float s1,
-                                          const floatx4 (&R0)[4], const floatx4 (&R1)[4], float4 (&pre)[PFP],
+                                          const floatx4 (&H0)[NA], const floatx4 (&H1)[NA], float4 (&pre)[PFP],
                                           const NextFr &nx_end) {
+    static_assert(NA == (ZN ? 4 : 8), "U_i (zero-node form) or H_i");
     using C = WalkConsts<NQE, NTD>;
     using LY = WalkLay<NQE>;
     const EncW &P = a.P;
@@ -1293,13 +1297,19 @@ __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsr
     s1 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw1));
     const float mx = fmaxf(s0, s1), e0 = expf(s0 - mx), e1 = expf(s1 - mx), sum = e0 + e1;
     const float al0 = e0 / sum, al1 = e1 / sum;
+    // alpha is uniform over a column's 4 lane groups (score_dot ends in col_sum): Hm is in H's layout
+    floatx4 Hm[NA];
+#pragma unroll
+    for (int t = 0; t < NA; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Hm[t][r] = al0 * H0[t][r] + al1 * H1[t][r];
+    }
     floatx4 X[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const floatx4 p2 = st.P2[t][lane];
+    for (int t = 0; t < 4; ++t) X[t] = st.P2[t][lane];
+    cgemm_p<4, NA, NA, ZN ? FoldLay::A1GZ : FoldLay::A1G>(wr, Hm, X, pre, pair_first<4>(FoldLay::M1A2 / 4));
 #pragma unroll
-        for (int r = 0; r < 4; ++r) X[t][r] = relu(p2[r] + (al0 * R0[t][r] + al1 * R1[t][r]));
-    }
+    for (int t = 0; t < 4; ++t) X[t] = relu4(X[t]);
     // MLP.0 over [attention out | one-hot(cat)] (compute_catogory_feautres :308-315): the one-hot column and
     // the biases come in as the accumulators' initial value, row cat of tc (row 12 for a padding column)
     const int32_t c = (valid && hi.v && hi.c >= 0 && hi.c < 12) ? hi.c : 12;
@@ -1350,6 +1360,7 @@ __device__ __forceinline__ float score_dot(const Stash &st, const floatx4 (&H)[8
 template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false>
 __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk_kernel(WalkArgs a) {
     using C = WalkConsts<NQE, NTD>;
+    constexpr int NA = ZN ? 4 : 8;                      // tiles of a position's hidden vector (ZN: U alone)
     const EncW &P = a.P;
     const int lane = threadIdx.x & 63, col = lane & 15;
     const int32_t NS = a.W / a.M;
@@ -1407,7 +1418,9 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     Stash &st = stash[threadIdx.x >> 6];
     // every weight fragment off one buffer resource (WalkLay offsets from the folded region's base)
     const auto wr = wrsrc(P.kv.w);
-    floatx4 R0[4];                                      // A1G H_0, carried to the position-1 pass
+    // position 0's hidden vector (U_0 in the zero-node form) and score, carried to the position-1 pass; every
+    // position-0 pass overwrites both, so no unit reads another's
+    floatx4 H0[NA];
     float s0 = 0.f;
     const int n_pass = SPLIT ? 3 : 1 + 2 * a.M;
     PosIn cur = load_pos(a, eg * a.W + (int64_t)j * a.M, 2, valid);
@@ -1486,9 +1499,13 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
         floatx4 H[8];
         unsigned long long T[10];
         TM_STAMP(0);
+        // event_gcn hands off the pass's next GEMM's first fragments: the slot pass's A1D, the position-1 pass's
+        // A1G (consumed in the head, after the softmax); a position-0 pass has no GEMM left, so the next pass's
+        // lin_event fragments
+        const NextFr nx_pos = ZN ? pair_first<4>(p == 2 ? FoldLay::A1DZ / 4 : FoldLay::A1GZ / 4)
+                                 : pair_first<8>(p == 2 ? FoldLay::A1D / 4 : FoldLay::A1G / 4);
         encode_position<NQE, NTD, SEF, QE0, ZN>(a, wr, cs, cur, ef, et, extra, p, H, pre,
-                                            ZN ? pair_first<4>(p == 2 ? FoldLay::A1DZ / 4 : FoldLay::A1GZ / 4)
-                                               : pair_first<8>(p == 2 ? FoldLay::A1D / 4 : FoldLay::A1G / 4), T);
+                                                p == 0 ? lin0 : nx_pos, T);
         if constexpr (QE0 == 0) load_ef(a, nxt.edge(), ef);
         else load_et<QE0>(a, nxt.edge(), et);
         cur = nxt;
@@ -1548,23 +1565,23 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             for (int t = 0; t < 4; ++t) st.P2[t][lane] = P2[t];
             st.cw[lane] = cw;
         }
-        floatx4 R[4];
+        // score = V . H_p + cw (VALU); A1G runs once per walk, in the head, on alpha_0 H_0 + alpha_1 H_1
+        // (stamp 7: the slot pass's is above; a position pass's "folded gemms" phase is the score alone, the
+        // A1G GEMM counts in the position-1 pass's head phase)
         float s = 0.f;
         if (p != 2) {
-            // R = A1G H_p (attention.MLP.0 of W2's output for this position), score = V . H_p + cw
-#pragma unroll
-            for (int t = 0; t < 4; ++t) R[t] = floatx4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (ZN) cgemm_p<4, 4, 4, FoldLay::A1GZ>(wr, Uv, R, pre, p == 1 ? pair_first<4>(FoldLay::M1A2 / 4) : lin0);
-            else cgemm_p<4, 8, 8, FoldLay::A1G>(wr, H, R, pre, p == 1 ? pair_first<4>(FoldLay::M1A2 / 4) : lin0);
             s = score_dot<ZN>(st, H);
             TM_STAMP(7);
-            if (p == 0) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) R0[t] = R[t];
-                s0 = s;
-            }
         }
-        if (p == 1) walk_head<NQE, NTD>(a, wr, cs, gw, valid, hi, st, s0, s, R0, R, pre, lin0);
+        if (p == 0) {
+#pragma unroll
+            for (int t = 0; t < NA; ++t) H0[t] = H[t];
+            s0 = s;
+        }
+        if (p == 1) {
+            if constexpr (ZN) walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, Uv, pre, lin0);
+            else walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, H, pre, lin0);
+        }
         TM_STAMP(8);
 #ifdef TM_TRACE
         if (lane == 0 && trw < 8192 && trn < 2 && pass < 7) g_tr[trw][2 + 7 * trn + pass] = __builtin_amdgcn_s_memrealtime();

@@ -36,7 +36,7 @@ struct EncW {
     // G = W2 blockdiag(g2,g2), beta = W2 [bg2;bg2] + b2 (Q_i = W2 F_i + b2 = G H_i + beta).  The score
     // Wp . Q_i = V . H_i + cw with V = G^T Wp = kv H_2 + v0 (kv = G^T W1D, v0 = G^T b1d) and
     // cw = Wp . beta = u . H_2 + c0 (u = W1D^T beta, c0 = b1d . beta); attention.MLP.0 of the
-    // attention output = P2 + alpha_0 R_0 + alpha_1 R_1 with P2 = A1D H_2 + cp, R_i = A1G H_i
+    // attention output = P2 + A1G (alpha_0 H_0 + alpha_1 H_1) with P2 = A1D H_2 + cp
     // (A1D = a1 blockdiag(g2,g2), A1G = a1 G, cp = a1 [bg2;bg2] + a1 beta + ba1; alpha_0 + alpha_1 = 1);
     // M1A2 = MLP.0[:, :h] a2, tc[c] = MLP.0[:, h + c] + bm1 + MLP.0[:, :h] ba2 (row 12: no category).
     Lin kv, a1d, a1g, m1a2;

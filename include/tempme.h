@@ -535,6 +535,65 @@ int tm_tgn_attn_fwd(const tm_tgn_attn *a, float *z, float *stats, void *stream);
 int tm_tgn_attn_bwd(const tm_tgn_attn *a, const float *stats, const float *gz, float *d_ew_parts, float *d_node,
                     void *stream);
 
+/* ---------------------------------------------------------------- TGAT base model (consumer of the path)
+ * One attention pass of the base TGAT (TGAT/TGAT.py: forward_msg_layer :678-706 -> AttnModel :362-386 ->
+ * MultiHeadAttention :110-137 -> ScaledDotProductAttention :64-80), the part that touches every
+ * neighbour, in the folded form of tm_tgn_attn: per source row r and head h
+ *     s_j = (qf[r,h] . key[r,j]) / temperature,   s_j = -1e10 where mask_node[m,j] == 0
+ *     z[r,h] = sum_j softmax(s)_j * ew[m,j] * key[r,j]
+ * with key[r,j] = [node (d_node) | edge (d_edge) | cos(fl(fl(dt[r,j]*time_w) + time_b)) (d_time)]: TGAT's
+ * TimeEncode (:230-241) multiplies and then adds in place, two fp32 roundings, where TGN's Linear rounds
+ * once.  m = base + ((r-base)*n_head + h) % seg with seg = seg_rows (or rows), the .repeat(n_head,1,1)
+ * pairing of :128-130 inside the rows of one forward_msg call; m = r when head_major_rows is 0.
+ * qf[r,h] = (W_k,h^T W_q,h) query[r] with query = [src | 0 | src_t]; d_key = d_node + d_edge + d_time is
+ * the model width (each head projects it to d_key / n_head), temperature = sqrt(d_key / n_head).
+ * Limits: n_head <= 4, d_key <= 512 (else TM_E_UNSUPPORTED).  Out-of-range node / edge ids set *err_flag
+ * and read row 0.  Field meanings as in tm_tgn_attn. */
+typedef struct {
+    int32_t rows, n_ngh, n_head;
+    int32_t d_node, d_edge, d_time;
+    int32_t node_rows, edge_rows;
+    int32_t head_major_rows;
+    int32_t seg_rows;
+    float temperature;
+    const float *node_tab;                /* node_idx != NULL: [node_rows, d_node] table; else dense [rows*n_ngh, d_node] */
+    const int32_t *node_idx;              /* [rows*n_ngh] or NULL */
+    const float *edge_tab;                /* edge_idx != NULL: [edge_rows, d_edge] table; else dense [rows*n_ngh, d_edge] */
+    const int32_t *edge_idx;              /* [rows*n_ngh] or NULL */
+    const float *dt;                      /* [rows*n_ngh] time deltas (f32) */
+    const float *time_w, *time_b;         /* [d_time] TimeEncode basis_freq and phase */
+    const int32_t *mask_node;             /* [rows*n_ngh]; 0 = padding (masked) */
+    const float *ew;                      /* [rows*n_ngh] explanation weights or NULL (= 1) */
+    const float *qf;                      /* [rows, n_head*d_key] folded queries */
+    int32_t *err_flag;                    /* nullable device flag: set to TM_E_ARG on an out-of-range index */
+} tm_tgat_attn;
+
+/* forward: z [rows, n_head*d_key], stats [rows, n_head, 2] (softmax max and sum, for the backward) */
+int tm_tgat_attn_fwd(const tm_tgat_attn *a, float *z, float *stats, void *stream);
+/* backward given gz = dL/dz.  d_ew_parts [rows*n_head, n_ngh]: the contribution of pair q = r*n_head + h to
+ * d ew[m(q), j] (the caller sums the n_head contributions of each row).  d_node (nullable; dense node_tab
+ * only) [rows*n_ngh, d_node] = dL/d node feature.  d_qf (nullable) [rows, n_head*d_key] = dL/d qf:
+ * d_qf[r,h] = (1/temperature) sum_j ds_j key[r,j], ds_j = p_j (ew_j c_j - S_h) with c_j = gz[r,h].key[r,j],
+ * S_h = sum_j p_j ew_j c_j, and ds_j = 0 where masked (a masked score is a constant). */
+int tm_tgat_attn_bwd(const tm_tgat_attn *a, const float *stats, const float *gz, float *d_ew_parts, float *d_node,
+                     float *d_qf, void *stream);
+
+/* The layer tail after the attention (AttnModel :383-385, MultiHeadAttention :133-135, MergeLayer :24-34)
+ * for `rows` source rows, fused, on fp32 MFMA:
+ *     u   = z G^T + fc_b + query                z [rows, n_head*d_key], G = fc W_v [d_key, n_head*d_key]
+ *     h   = LayerNorm(u) * ln_w + ln_b          over d_key, eps 1e-5
+ *     out = W21 relu(W11 h + b11) + b21 + W22 relu(W12 src + b12) + b22       src = query[:, :feat]
+ * Every weight is passed TRANSPOSED ([in][out] row-major): gt [n_head*d_key, d_key], w11t [d_key, feat],
+ * w12t / w21t / w22t [feat, feat].  out [rows, feat].  feat <= d_key <= 512, and the row tile
+ * (16 rows of d_key + 2 max(feat, 128) padded columns) must fit 64 KiB of LDS, else TM_E_UNSUPPORTED. */
+typedef struct {
+    int32_t rows, n_head, d_key, feat;
+    const float *z, *query;
+    const float *gt, *fc_b, *ln_w, *ln_b;
+    const float *w11t, *b11, *w12t, *b12, *w21t, *b21, *w22t, *b22;
+} tm_tgat_merge;
+int tm_tgat_merge_fwd(const tm_tgat_merge *a, float *out, void *stream);
+
 /* threshold_test masking (temp_exp_main.py:153-181, tgn branch): for group g and row r,
  * sel = torch.topk(imp[r], k_of_group[g], largest=False).indices as the reference computes it on the
  * CPU -- the index set std::nth_element (or std::partial_sort when 64*k <= n) leaves in front of

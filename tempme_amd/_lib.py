@@ -40,7 +40,7 @@ EXPORTS = (
     "tm_encoder_workspace_bytes",
     "tm_encoder_fwd", "tm_encoder_fwd_tab", "tm_encoder_train_supported", "tm_encoder_train_fwd", "tm_encoder_bwd", "tm_encoder_wgrad", "tm_wgrad",
     "tm_explain_train_fwd", "tm_explain_train_fwd_pad", "tm_explain_train_bwd", "tm_kl_loss", "tm_edge_importance", "tm_edge_gate_table",
-    "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
+    "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_tgat_attn_fwd", "tm_tgat_attn_bwd", "tm_tgat_merge_fwd", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
     "tm_mask_least_important", "tm_profile_enable", "tm_profile_sync", "tm_profile_entry",
     "tm_beta_params", "tm_beta_rsample_bwd", "tm_adam_step", "tm_copy_many", "tm_host_register", "tm_host_unregister",
     "tm_stage_cast",
@@ -61,6 +61,18 @@ class TgnAttn(C.Structure):
                 ("node_tab", C.c_void_p), ("node_idx", C.c_void_p), ("edge_tab", C.c_void_p),
                 ("edge_idx", C.c_void_p), ("dt", C.c_void_p), ("time_w", C.c_void_p), ("time_b", C.c_void_p),
                 ("mask_node", C.c_void_p), ("ew", C.c_void_p), ("qf", C.c_void_p), ("err_flag", C.c_void_p)]
+
+
+class TgatAttn(C.Structure):
+    """tm_tgat_attn (include/tempme.h): the layout of tm_tgn_attn."""
+    _fields_ = list(TgnAttn._fields_)
+
+
+class TgatMerge(C.Structure):
+    """tm_tgat_merge (include/tempme.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("rows", "n_head", "d_key", "feat")] + \
+               [(n, C.c_void_p) for n in ("z", "query", "gt", "fc_b", "ln_w", "ln_b", "w11t", "b11", "w12t", "b12",
+                                          "w21t", "b21", "w22t", "b22")]
 
 
 class GmEmbedArgs(C.Structure):
@@ -197,6 +209,9 @@ def _sig(L):
     L.tm_edge_importance_gf3_bern.argtypes = [i32, i32, i32] + [vp] * 26
     L.tm_tgn_attn_fwd.argtypes = [C.POINTER(TgnAttn), vp, vp, vp]
     L.tm_tgn_attn_bwd.argtypes = [C.POINTER(TgnAttn), vp, vp, vp, vp, vp]
+    L.tm_tgat_attn_fwd.argtypes = [C.POINTER(TgatAttn), vp, vp, vp]
+    L.tm_tgat_attn_bwd.argtypes = [C.POINTER(TgatAttn), vp, vp, vp, vp, vp, vp]
+    L.tm_tgat_merge_fwd.argtypes = [C.POINTER(TgatMerge), vp, vp]
     L.tm_mask_least_important.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
     L.tm_profile_enable.argtypes = [C.c_int]
     L.tm_beta_params.argtypes = [vp, i64, vp, vp, vp]

@@ -243,8 +243,9 @@ class TempME(nn.Module):
         self.final_linear = nn.Linear(2 * self.hid_dim, self.hid_dim)
         self.node_emd_dim = self.hid_dim + 12 + self.node_dim if self.if_cat else self.hid_dim + self.node_dim
         self.affinity_score = _MergeLayer(self.node_emd_dim, self.node_emd_dim)
-        self.edge_raw_embed = base.edge_raw_features
-        self.node_raw_embed = base.node_raw_features
+        # TGN and GraphMixer name their feature tables *_raw_features, TGAT *_raw_embed (TGAT.py:413-414)
+        self.edge_raw_embed = base.edge_raw_features if hasattr(base, "edge_raw_features") else base.edge_raw_embed
+        self.node_raw_embed = base.node_raw_features if hasattr(base, "node_raw_features") else base.node_raw_embed
         self.time_encoder = TimeEncode(expand_dim=self.time_dim)
         self.null_model = (null_model if null_model is not None
                            else get_null_distribution(data, data_dir=data_dir, seed=seed, device=device))

@@ -1,5 +1,5 @@
 """Fidelity evaluation of an explanation on the base model: ``threshold_test``
-(temp_exp_main.py:153-272, tgn and graphmixer branches) on the HIP device.
+(temp_exp_main.py:153-272, tgn, graphmixer and tgat branches) on the HIP device.
 
 For each sparsity ratio the reference keeps the top ``ceil(ratio * (N + N^2))`` subgraph entries by
 explanation score, zeroes the node ids of the rest (torch.topk(largest=False) + np.put_along_axis),
@@ -85,12 +85,41 @@ def masked_contrast_graphmixer(base_model, explanation, src_l_cut, dst_l_cut, ds
     return score[:, :B], score[:, B:]
 
 
+def masked_contrast_tgat(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
+                         subgraph_tgt, subgraph_bgd, n_degree, ratios):
+    """tgat branch (temp_exp_main.py:216-250): the explanation is the per-side 6-list
+    [src0, src1, tgt0, tgt1, bgd0, bgd1]; [hop-1 | hop-2] records masked, then contrast without weights.
+    All ratios in one batch: every (ratio, side) is one forward_msg call of B rows, a segment of its own."""
+    dev = base_model._dev()
+    B, N, G = len(src_l_cut), n_degree, len(ratios)
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    stacked = [torch.cat([explanation[2 * s + h].to(dev) for s in range(3)], dim=0) for h in (0, 1)]
+    masked = _masked_nodes(stacked, sgs, N, ratios, dev)                              # [G, 3B, ne]
+    roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_l_cut, dst_l_cut, dst_l_fake)])
+    n1 = masked[:, :, :N].reshape(G * 3 * B, N)
+    n2 = masked[:, :, N:].reshape(G * 3 * B, N * N)
+
+    def rep(i, h, dtype):
+        x = torch.cat([_as_dev(sg[i][h], dev, dtype) for sg in sgs], dim=0)
+        return x.repeat(G, 1)
+    emb = base_model.node_embeddings([roots.repeat(G), n1, n2], [rep(1, 0, torch.int32), rep(1, 1, torch.int32)],
+                                     [rep(2, 0, torch.float64), rep(2, 1, torch.float64)], ts_l_cut,
+                                     n_segments=3 * G)
+    emb = emb.view(G, 3, B, -1)
+    s, d, n = emb[:, 0], emb[:, 1], emb[:, 2]
+    x1 = torch.cat([s, s], dim=1).reshape(G * 2 * B, -1)
+    x2 = torch.cat([d, n], dim=1).reshape(G * 2 * B, -1)
+    score = base_model.affinity(x1, x2).view(G, 2 * B)
+    return score[:, :B], score[:, B:]
+
+
 def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, e_l_cut,
                    pos_out_ori, neg_out_ori, y_ori, subgraph_src, subgraph_tgt, subgraph_bgd):
     """temp_exp_main.py:153-272 -> (aps_AUC, auc_AUC, acc_AUC, fid_prob_AUC, fid_logit_AUC)."""
-    fns = {"tgn": masked_contrast, "graphmixer": masked_contrast_graphmixer}
+    fns = {"tgn": masked_contrast, "graphmixer": masked_contrast_graphmixer, "tgat": masked_contrast_tgat}
     if args.base_type not in fns:
-        raise NotImplementedError(f"threshold_test for base_type {args.base_type!r}: tgn and graphmixer are built")
+        raise NotImplementedError(f"threshold_test for base_type {args.base_type!r}: tgn, graphmixer and tgat "
+                                  "are built")
     with torch.no_grad():
         pos, neg = fns[args.base_type](base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut,
                                        subgraph_src, subgraph_tgt, subgraph_bgd, args.n_degree, list(args.ratios))

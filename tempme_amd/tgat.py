@@ -1,0 +1,447 @@
+"""Drop-in base ``TGAT`` (TGAT/TGAT.py) for the consumer side of the explanation path.
+
+With ``--base_type tgat`` TempME's loops hand per-side explanation weights to the frozen base model:
+``base_model.contrast(src, dst, fake, ts, e_idx, sg_src, sg_tgt, sg_bgd, test=True, if_explain=True,
+exp_weights=[[imp_src, imp_tgt], [imp_src, imp_bgd]])`` (temp_exp_main.py:609-616), every ``imp`` a
+``(hop-1 [B, N], hop-2 [B, N^2])`` pair.  This module keeps the reference's constructor, parameter names
+(a reference ``state_dict`` loads as is), construction order (``torch.manual_seed(s); TGAT(...)`` draws the
+reference's initial weights) and the ``contrast`` / ``get_node_emb`` / ``grab_subgraph`` signatures.
+
+What the reference computes per side with ``num_layers = 2`` (forward_msg :607-619):
+  1. ``attn_model_list[0]``: the B roots over their raw hop-1 neighbours, weights exp[0]      -> h0'
+  2. ``attn_model_list[0]``: the B*N hop-1 nodes over their raw hop-2 neighbours, weights exp[1] -> h1'
+  3. ``attn_model_list[1]``: h0' over h1' (dense), hop-1 edge and time features, weights exp[0] again.
+The query of a pass is ``[src | 0 (d_edge) | src_t]`` with src_t = TimeEncode(0) for roots and
+TimeEncode(cut - t1) for the hop-1 rows of pass 2.
+
+Here every pass is one launch of ``tgat_attn_fwd_kernel`` (csrc/tgat_attn.hip) over the rows of all sides,
+the sides being segments of ``seg_rows`` = B (or B*N) rows so the reference's head-major mask / weight
+pairing stays inside one forward_msg call.  The per-neighbour projections fold into per-row ones
+(qf = W_k^T W_q query before the kernel, G = fc W_v after it, as tgn.py).  The layer tail (G z + residual,
+LayerNorm, the two-branch MergeLayer) runs as torch ops on the device (differentiable); with
+``model.fused_tail = True`` a contrast that needs no gradient runs it as one fused fp32-MFMA kernel
+(``tm_tgat_merge_fwd``) instead, which is built and tested but slower at the metric's shape, so off by default.  Gradients reach the explanation weights of all
+three passes: ``tm_tgat_attn_bwd`` returns d ew, the gradient of the dense neighbour table (h1') and the
+gradient of the folded query (through h0').  The base model is frozen: its parameters get no .grad.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib as L
+from .tgn import _as_dev
+
+
+# ------------------------------------------------------------------ modules (parameter layout)
+class MergeLayer(nn.Module):
+    """TGAT.py:9-34: fc21(relu(fc11(x1))) + fc22(relu(fc12(x2)))."""
+
+    def __init__(self, dim1, dim2, dim3, dim4, non_linear=True):
+        super().__init__()
+        self.fc11 = nn.Linear(dim1, dim3)
+        self.fc12 = nn.Linear(dim2, dim3)
+        self.fc21 = nn.Linear(dim3, dim4)
+        self.fc22 = nn.Linear(dim3, dim4)
+        self.act = nn.ReLU()
+        nn.init.xavier_normal_(self.fc11.weight)
+        nn.init.xavier_normal_(self.fc21.weight)
+        nn.init.xavier_normal_(self.fc12.weight)
+        nn.init.xavier_normal_(self.fc22.weight)
+
+    def forward(self, x1, x2):
+        return self.fc22(self.act(self.fc12(x2))) + self.fc21(self.act(self.fc11(x1)))
+
+
+class MergeLayer_final(nn.Module):
+    """TGAT.py:37-52: fc2(relu(fc1([x1 | x2])))."""
+
+    def __init__(self, dim1, dim2, dim3, dim4):
+        super().__init__()
+        self.fc1 = nn.Linear(dim1 + dim2, dim3)
+        self.fc2 = nn.Linear(dim3, dim4)
+        self.act = nn.ReLU()
+        nn.init.xavier_normal_(self.fc1.weight)
+        nn.init.xavier_normal_(self.fc2.weight)
+
+    def forward(self, x1, x2):
+        return self.fc2(self.act(self.fc1(torch.cat([x1, x2], dim=1))))
+
+
+class MultiHeadAttention(nn.Module):
+    """Parameters of TGAT.py:83-107 (d_k = d_v = d_model // n_head, no projection bias)."""
+
+    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
+        super().__init__()
+        self.n_head, self.d_k, self.d_v = n_head, d_k, d_v
+        self.w_qs = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_ks = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_vs = nn.Linear(d_model, n_head * d_v, bias=False)
+        nn.init.normal_(self.w_qs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_k)))
+        nn.init.normal_(self.w_ks.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_k)))
+        nn.init.normal_(self.w_vs.weight, mean=0, std=np.sqrt(2.0 / (d_model + d_v)))
+        self.temperature = float(np.power(d_k, 0.5))
+        self.layer_norm = nn.LayerNorm(d_model)
+        self.fc = nn.Linear(n_head * d_v, d_model)
+        nn.init.xavier_normal_(self.fc.weight)
+        self.dropout = nn.Dropout(dropout)
+
+
+class TimeEncode(nn.Module):
+    """TGAT.py:220-241: cos(ts * basis_freq + phase), the multiply and the add rounded separately."""
+
+    def __init__(self, expand_dim, factor=5):
+        super().__init__()
+        self.time_dim = expand_dim
+        self.factor = factor
+        self.basis_freq = nn.Parameter(torch.from_numpy(1 / 10 ** np.linspace(0, 9, self.time_dim)).float())
+        self.phase = nn.Parameter(torch.zeros(self.time_dim).float())
+
+    def forward(self, ts):
+        map_ts = ts.unsqueeze(-1) * self.basis_freq.view(1, 1, -1)
+        map_ts = map_ts + self.phase.view(1, 1, -1)
+        return torch.cos(map_ts)
+
+
+class AttnModel(nn.Module):
+    """TGAT.py:317-360 (attn_mode 'prod')."""
+
+    def __init__(self, feat_dim, edge_dim, time_dim, model_dim, attn_mode="prod", n_head=2, drop_out=0.1):
+        super().__init__()
+        self.feat_dim, self.edge_dim, self.time_dim, self.model_dim = feat_dim, edge_dim, time_dim, model_dim
+        self.merger = MergeLayer(self.model_dim, feat_dim, feat_dim, feat_dim)
+        assert self.model_dim % n_head == 0
+        self.attn_mode = attn_mode
+        self.multi_head_target = MultiHeadAttention(n_head, d_model=self.model_dim, d_k=self.model_dim // n_head,
+                                                    d_v=self.model_dim // n_head, dropout=drop_out)
+
+
+# ------------------------------------------------------------------ the HIP attention op
+class _TgatAttnFn(torch.autograd.Function):
+    """z = tm_tgat_attn_fwd(...); backward through tm_tgat_attn_bwd: explanation weights, the dense
+    neighbour table (pass 3's h1') and the folded query (pass 3's h0')."""
+
+    @staticmethod
+    def forward(ctx, qf, ngh_dense, ew, spec):
+        dev = qf.device
+        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
+        desc = _desc(spec, qf, ngh_dense, ew)
+        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
+        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
+        if R:
+            L.check(L.lib().tm_tgat_attn_fwd(L.C.byref(desc), L.ptr(z), L.ptr(stats), L.stream_ptr(dev)),
+                    "TGAT attention")
+        ctx.spec = spec
+        ctx.save_for_backward(qf, ngh_dense, ew, stats)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        qf, ngh_dense, ew, stats = ctx.saved_tensors
+        spec = ctx.spec
+        R, H, N = spec["rows"], spec["n_head"], spec["n_ngh"]
+        dev = gz.device
+        gz = gz.contiguous().float()
+        want_node = ngh_dense is not None and ctx.needs_input_grad[1]
+        parts = torch.empty((R * H, N), dtype=torch.float32, device=dev)
+        d_node = torch.empty_like(ngh_dense) if want_node else None
+        d_qf = torch.empty_like(qf) if ctx.needs_input_grad[0] else None
+        if R:
+            desc = _desc(spec, qf, ngh_dense, ew)
+            L.check(L.lib().tm_tgat_attn_bwd(L.C.byref(desc), L.ptr(stats), L.ptr(gz), L.ptr(parts), L.ptr(d_node),
+                                             L.ptr(d_qf), L.stream_ptr(dev)), "TGAT attention backward")
+        d_ew = None
+        if ew is not None and ctx.needs_input_grad[2]:
+            # pair q = r*H + h contributes to weight row base + ((r-base)*H + h) % seg of its segment
+            seg = spec.get("seg_rows", 0) or R
+            if spec["head_major"]:
+                d_ew = parts.view(R // seg, H, seg, N).sum(1)
+            else:
+                d_ew = parts.view(R, H, N).sum(1)
+            d_ew = d_ew.reshape(ew.shape)
+        return d_qf, d_node, d_ew, None
+
+
+def _desc(spec, qf, ngh_dense, ew):
+    a = L.TgatAttn()
+    a.rows, a.n_ngh, a.n_head = spec["rows"], spec["n_ngh"], spec["n_head"]
+    a.d_node, a.d_edge, a.d_time = spec["d_node"], spec["d_edge"], spec["d_time"]
+    a.node_rows, a.edge_rows = spec["node_rows"], spec["edge_rows"]
+    a.head_major_rows = 1 if spec["head_major"] else 0
+    a.seg_rows = spec.get("seg_rows", 0)
+    a.temperature = spec["temperature"]
+    a.node_tab = (ngh_dense if ngh_dense is not None else spec["node_tab"]).data_ptr()
+    a.node_idx = spec["node_idx"].data_ptr() if spec["node_idx"] is not None else None
+    a.edge_tab = spec["edge_tab"].data_ptr()
+    a.edge_idx = spec["edge_idx"].data_ptr()
+    a.dt = spec["dt"].data_ptr()
+    a.time_w, a.time_b = spec["time_w"].data_ptr(), spec["time_b"].data_ptr()
+    a.mask_node = spec["mask_node"].data_ptr()
+    a.ew = ew.data_ptr() if ew is not None else None
+    a.qf = qf.data_ptr()
+    a.err_flag = spec["err"].data_ptr()
+    return a
+
+
+def merge_fwd(z, query, lw, feat):
+    """The fused layer tail (tm_tgat_merge_fwd) on a packed attention model ``lw`` -> [rows, feat]."""
+    dev = z.device
+    R, dk = query.shape
+    m = L.TgatMerge()
+    m.rows, m.n_head, m.d_key, m.feat = R, lw["H"], dk, feat
+    z, query = z.contiguous(), query.contiguous()
+    m.z, m.query = z.data_ptr(), query.data_ptr()
+    for f, k in (("gt", "Gt"), ("fc_b", "fcb"), ("ln_w", "lnw"), ("ln_b", "lnb"), ("w11t", "w11t"), ("b11", "b11"),
+                 ("w12t", "w12t"), ("b12", "b12"), ("w21t", "w21t"), ("b21", "b21"), ("w22t", "w22t"), ("b22", "b22")):
+        setattr(m, f, lw[k].data_ptr())
+    out = torch.empty((R, feat), dtype=torch.float32, device=dev)
+    L.check(L.lib().tm_tgat_merge_fwd(L.C.byref(m), L.ptr(out), L.stream_ptr(dev)), "TGAT layer tail")
+    return out
+
+
+def merge_torch(z, query, lw, feat):
+    """The same tail as torch ops (differentiable; the reference's order of operations)."""
+    out = torch.addmm(lw["fcb"], z, lw["Gt"])
+    h = F.layer_norm(out + query, (query.shape[1],), lw["lnw"], lw["lnb"], 1e-5)
+    x1 = torch.addmm(lw["b21"], F.relu(torch.addmm(lw["b11"], h, lw["w11t"])), lw["w21t"])
+    x2 = torch.addmm(lw["b22"], F.relu(torch.addmm(lw["b12"], query[:, :feat], lw["w12t"])), lw["w22t"])
+    return x2 + x1
+
+
+def pack_attn_model(am, dev):
+    """Folded, device-resident weights of one AttnModel: P = W_k^T W_q and G = fc W_v per head, folded in
+    fp64 and stored in fp32; the tail's matrices transposed ([in][out]) as tm_tgat_merge_fwd reads them."""
+    f32, f64 = torch.float32, torch.float64
+    mh, mg = am.multi_head_target, am.merger
+    H, dh = mh.n_head, mh.d_k
+    dm = mh.w_qs.weight.shape[1]
+    wq = mh.w_qs.weight.detach().to(dev, f64).view(H, dh, dm)
+    wk = mh.w_ks.weight.detach().to(dev, f64).view(H, dh, dm)
+    wv = mh.w_vs.weight.detach().to(dev, f64).view(H, dh, dm)
+    fc = mh.fc.weight.detach().to(dev, f64).view(dm, H, dh)
+    P = torch.einsum("hoi,hoq->hiq", wk, wq).reshape(H * dm, dm)          # qf = P query  [H*dm]
+    G = torch.einsum("qho,hoi->qhi", fc, wv).reshape(dm, H * dm)          # fc(...) = G z
+
+    def t(lin):
+        return lin.weight.detach().to(dev, f32).t().contiguous()
+
+    def b(lin):
+        return lin.bias.detach().to(dev, f32).contiguous()
+    return dict(Pt=P.t().to(f32).contiguous(), Gt=G.t().to(f32).contiguous(), fcb=b(mh.fc),
+                lnw=mh.layer_norm.weight.detach().to(dev, f32).contiguous(),
+                lnb=mh.layer_norm.bias.detach().to(dev, f32).contiguous(),
+                w11t=t(mg.fc11), b11=b(mg.fc11), w12t=t(mg.fc12), b12=b(mg.fc12),
+                w21t=t(mg.fc21), b21=b(mg.fc21), w22t=t(mg.fc22), b22=b(mg.fc22),
+                H=H, dk=dm, temperature=mh.temperature)
+
+
+# ------------------------------------------------------------------ the model
+class TGAT(nn.Module):
+    """TGAT/TGAT.py:389-423 constructor (same arguments, parameter names and initialisation order)."""
+
+    def __init__(self, n_feat, e_feat, num_neighbors, attn_mode="prod", use_time="time", attn_agg_method="attn",
+                 num_layers=3, n_head=4, drop_out=0.1, verbosity=1):
+        super().__init__()
+        if attn_agg_method != "attn":
+            raise NotImplementedError(f"attn_agg_method {attn_agg_method!r}: only 'attn' is built (the LSTM and "
+                                      "mean pools ignore the explanation weights)")
+        if attn_mode != "prod":
+            raise NotImplementedError(f"attn_mode {attn_mode!r}: only 'prod' is built (the map-based attention "
+                                      "takes no explanation weight in the reference)")
+        if use_time != "time":
+            raise NotImplementedError(f"use_time {use_time!r}: only the harmonic 'time' encoder is built")
+        if num_layers != 2:
+            raise NotImplementedError(f"num_layers {num_layers}: the explanation path samples 2-hop subgraphs, "
+                                      "so only num_layers=2 is built")
+        if n_head > 4:
+            raise NotImplementedError(f"n_head {n_head}: the attention kernels hold at most 4 heads")
+        self.verbosity = verbosity
+        self.num_neighbors, self.num_layers = num_neighbors, num_layers
+        self.ngh_finder = None
+        self.n_feat_th = nn.Parameter(torch.from_numpy(np.asarray(n_feat).astype(np.float32)), requires_grad=False)
+        self.e_feat_th = nn.Parameter(torch.from_numpy(np.asarray(e_feat).astype(np.float32)), requires_grad=False)
+        self.feat_dim = self.n_feat_th.shape[1]
+        self.e_feat_dim = self.e_feat_th.shape[1]
+        self.time_dim = self.feat_dim
+        self.model_dim = self.feat_dim + self.e_feat_dim + self.time_dim
+        if self.model_dim > 512:
+            raise NotImplementedError(f"model_dim {self.model_dim}: the attention kernels hold keys of at most 512")
+        self.dropout_p = drop_out
+        self.edge_raw_embed = nn.Embedding.from_pretrained(self.e_feat_th, padding_idx=0, freeze=True)
+        self.node_raw_embed = nn.Embedding.from_pretrained(self.n_feat_th, padding_idx=0, freeze=True)
+        self.time_encoder = TimeEncode(expand_dim=self.time_dim)
+        self.attn_model_list = nn.ModuleList([AttnModel(self.feat_dim, self.e_feat_dim, self.time_dim, self.model_dim,
+                                                        attn_mode=attn_mode, n_head=n_head, drop_out=drop_out)
+                                              for _ in range(self.num_layers)])
+        self.affinity_score = MergeLayer_final(self.feat_dim, self.feat_dim, self.feat_dim, 1)
+        # the reference pairs attention rows with mask / explanation rows head-major through
+        # .repeat(n_head, 1, 1) (TGAT.py:128-130); False pairs row r with row r
+        self.head_major_rows = True
+        # the layer tail of a contrast that needs no gradient: True = the fused MFMA kernel (tm_tgat_merge_fwd),
+        # False = the torch ops.  The torch ops are the default: at the metric's shape the fused kernel measured
+        # 0.51 ms against 0.15 ms for the 6,000-row pass (DESIGN.md "TGAT contrast")
+        self.fused_tail = False
+        self._pack_cache = None
+        self._pack_key = None
+
+    # -------------------------------------------------------------- device pack
+    def _dev(self):
+        p = self.n_feat_th
+        return L.require_device(p.device if p.device.type == "cuda" else None)
+
+    def _pack(self):
+        """Device-resident tables and folded per-model weights, rebuilt when a parameter changes."""
+        dev = self._dev()
+        key = (dev, tuple((t.data_ptr(), t._version) for t in self.parameters()))
+        if self._pack_cache is not None and self._pack_key == key:
+            return self._pack_cache
+        f32 = torch.float32
+        with torch.no_grad():
+            freq = self.time_encoder.basis_freq.detach().to(dev, f32).contiguous()
+            phase = self.time_encoder.phase.detach().to(dev, f32).contiguous()
+            aff = self.affinity_score
+            pack = dict(dev=dev, tab=self.n_feat_th.detach().to(dev, f32).contiguous(),
+                        etab=self.e_feat_th.detach().to(dev, f32).contiguous(), freq=freq, phase=phase,
+                        t0=torch.cos(torch.zeros_like(freq) * freq + phase),      # TimeEncode(0)
+                        models=[pack_attn_model(am, dev) for am in self.attn_model_list],
+                        a1w=aff.fc1.weight.detach().to(dev, f32), a1b=aff.fc1.bias.detach().to(dev, f32),
+                        a2w=aff.fc2.weight.detach().to(dev, f32), a2b=aff.fc2.bias.detach().to(dev, f32),
+                        err=torch.zeros(1, dtype=torch.int32, device=dev))
+        self._pack_cache, self._pack_key = pack, key
+        return pack
+
+    # -------------------------------------------------------------- forward pieces
+    def _attn_pass(self, pk, mi, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, ew, seg):
+        """One AttnModel.forward (TGAT.py:362-386) over R source rows -> [R, feat]."""
+        lw = pk["models"][mi]
+        H, dk, fd = lw["H"], lw["dk"], self.feat_dim
+        query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)      # [R, dk]
+        qf = (query @ lw["Pt"]).contiguous()                                             # [R, H*dk]
+        spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=fd, d_edge=self.e_feat_dim, d_time=self.time_dim,
+                    node_rows=pk["tab"].shape[0], edge_rows=pk["etab"].shape[0], head_major=self.head_major_rows,
+                    temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"],
+                    edge_idx=edge_idx, dt=dt, time_w=pk["freq"], time_b=pk["phase"], mask_node=mask_node,
+                    err=pk["err"], seg_rows=seg)
+        z = _TgatAttnFn.apply(qf, ngh_dense, ew, spec)
+        if self.fused_tail and not (torch.is_grad_enabled() and (z.requires_grad or query.requires_grad)):
+            return merge_fwd(z, query, lw, fd)
+        return merge_torch(z, query, lw, fd)
+
+    def _check_mode(self):
+        if self.training and self.dropout_p > 0:
+            raise NotImplementedError("TGAT in training mode with drop_out > 0: the attention and fc dropout of "
+                                      "the reference are not built (the frozen base model runs in eval mode)")
+
+    def node_embeddings(self, nodes, eids, times, cut_time, explain_weights=None, n_segments=1):
+        """forward_msg (TGAT.py:607-619) for stacked calls: nodes = [n0 [R], n1 [R, N], n2 [R, N^2]],
+        eids / times = [hop-1, hop-2], explain_weights = (hop-1 [R, N], hop-2 [R, N^2]) or None -> [R, feat].
+        The R rows are ``n_segments`` independent forward_msg calls of R / n_segments rows each (the sides
+        of a contrast, times the ratios of a threshold_test): every row gives the same result as in its own
+        call, the head-major pairing stays inside its segment.  cut_time: one time per row, or per row of
+        one segment (repeated)."""
+        self._check_mode()
+        pk = self._pack()
+        dev = pk["dev"]
+        i32, f64 = torch.int32, torch.float64
+        n0 = _as_dev(nodes[0], dev, torch.long).reshape(-1)
+        R = n0.shape[0]
+        n1 = _as_dev(nodes[1], dev, i32).reshape(R, -1).contiguous()
+        N = n1.shape[1]
+        n2 = _as_dev(nodes[2], dev, i32).reshape(R * N, N).contiguous()
+        e1 = _as_dev(eids[0], dev, i32).reshape(R, N).contiguous()
+        e2 = _as_dev(eids[1], dev, i32).reshape(R * N, N).contiguous()
+        cut = _as_dev(cut_time, dev, f64).reshape(-1)
+        if R % n_segments:
+            raise AssertionError("rows must split evenly into n_segments")
+        seg = R // n_segments
+        if cut.shape[0] == seg and seg != R:
+            cut = cut.repeat(n_segments)
+        if cut.shape[0] != R:
+            raise AssertionError("cut_time must give one time per row (or per row of one segment)")
+        t1 = _as_dev(times[0], dev, f64).reshape(R, N)
+        t2 = _as_dev(times[1], dev, f64).reshape(R, N, N)
+        dt1 = (cut.view(R, 1) - t1).float().contiguous()                   # retrieve_time_features :653-666
+        dt2 = (t1.view(R, N, 1) - t2).float().contiguous()
+        ew1 = ew2 = None
+        if explain_weights is not None:
+            ew1 = explain_weights[0].to(dev, torch.float32).reshape(R, N).contiguous()
+            ew2 = explain_weights[1].to(dev, torch.float32).reshape(R * N, N).contiguous()
+        tab, freq, phase = pk["tab"], pk["freq"], pk["phase"]
+        t_root = pk["t0"].expand(R, -1)
+        t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)             # two roundings (mul, then add)
+        h0 = self._attn_pass(pk, 0, tab[n0], t_root, R, N, n1, None, e1, dt1, n1, ew1, seg)
+        h1 = self._attn_pass(pk, 0, tab[n1.reshape(-1).long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N)
+        return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg)
+
+    def check_errors(self):
+        """Raise if a kernel saw an out-of-range node or edge index (synchronises)."""
+        pk = self._pack_cache
+        if pk is not None and int(pk["err"].item()) != 0:
+            pk["err"].zero_()
+            raise IndexError("TGAT: node or edge index out of range of the feature tables")
+
+    def _sides(self, roots, subgraphs, weights, cut_time):
+        """Stack the sides of a contrast into one node_embeddings call -> list of [B, feat]."""
+        self._check_mode()
+        dev = self._dev()
+        S = len(roots)
+        n0 = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in roots])
+
+        def cat(i, h, dtype):
+            return torch.cat([_as_dev(sg[i][h], dev, dtype) for sg in subgraphs])
+        ew = None
+        if weights is not None:
+            ew = [torch.cat([w[h].to(dev, torch.float32) for w in weights]) for h in (0, 1)]
+        emb = self.node_embeddings([n0, cat(0, 0, torch.int32), cat(0, 1, torch.int32)],
+                                   [cat(1, 0, torch.int32), cat(1, 1, torch.int32)],
+                                   [cat(2, 0, torch.float64), cat(2, 1, torch.float64)], cut_time, ew, n_segments=S)
+        B = emb.shape[0] // S
+        return list(emb.split(B)) if B > 0 else [emb[:0]] * S
+
+    # -------------------------------------------------------------- reference API
+    def affinity(self, x1, x2):
+        pk = self._pack()
+        h = F.relu(F.linear(torch.cat([x1, x2], dim=1), pk["a1w"], pk["a1b"]))
+        return F.linear(h, pk["a2w"], pk["a2b"])
+
+    def contrast(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, e_idx_l, subgraph_src, subgraph_tgt, subgraph_bgd,
+                 test=False, if_explain=False, exp_weights=None):
+        """TGAT.py:461-481 -> (pos_score [B, 1], neg_score [B, 1]).  The three (or four) forward_msg calls
+        run as segments of one launch per pass; the src side runs once when both pairs carry the same src
+        weights (the same objects, as temp_exp_main.py:613 builds them), twice otherwise."""
+        roots = [src_idx_l, tgt_idx_l, bgd_idx_l]
+        sgs = [subgraph_src, subgraph_tgt, subgraph_bgd]
+        if not if_explain:
+            s, t, b = self._sides(roots, sgs, None, cut_time_l)
+            s2 = s
+        else:
+            (w_s, w_t), (w_s2, w_b) = exp_weights[0], exp_weights[1]
+            same = w_s is w_s2 or (len(w_s) == len(w_s2) and all(x is y for x, y in zip(w_s, w_s2)))
+            if same:
+                s, t, b = self._sides(roots, sgs, [w_s, w_t, w_b], cut_time_l)
+                s2 = s
+            else:
+                s, t, s2, b = self._sides([src_idx_l, tgt_idx_l, src_idx_l, bgd_idx_l],
+                                          [subgraph_src, subgraph_tgt, subgraph_src, subgraph_bgd],
+                                          [w_s, w_t, w_s2, w_b], cut_time_l)
+        B = s.shape[0]
+        score = self.affinity(torch.cat([s, s2], dim=0), torch.cat([t, b], dim=0))
+        return score[:B], score[B:]
+
+    def get_node_emb(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, e_idx_l, subgraph_src, subgraph_tgt,
+                     subgraph_bgd, test=False):
+        """TGAT.py:507-519 -> (source, target, background) embeddings [B, feat] each."""
+        return tuple(self._sides([src_idx_l, tgt_idx_l, bgd_idx_l], [subgraph_src, subgraph_tgt, subgraph_bgd], None,
+                                 cut_time_l))
+
+    def set_neighbor_sampler(self, neighbor_sampler):
+        self.ngh_finder = neighbor_sampler
+
+    def grab_subgraph(self, src_idx_l, cut_time_l, e_idx_l=None):
+        """TGAT.py:603-605."""
+        return self.ngh_finder.find_k_hop(self.num_layers, src_idx_l, cut_time_l, num_neighbors=self.num_neighbors,
+                                          e_idx_l=e_idx_l)
+
+
+__all__ = ["TGAT", "AttnModel", "MultiHeadAttention", "MergeLayer", "MergeLayer_final", "TimeEncode",
+           "merge_fwd", "merge_torch", "pack_attn_model"]

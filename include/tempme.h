@@ -219,6 +219,41 @@ int tm_encoder_fwd_tab(const tm_weights *w, const float *n_feat, const float *e_
                        const float *ts3, const int32_t *cat, const double *cut, const float *cnt, void *workspace,
                        float *out_imp, void *stream);
 
+/* ---------------------------------------------------------------- motif-enhanced link prediction (device)
+ * compute_walk_importance (explainer_new.py:260-306) for n_groups groups of [B, W] walks (one group = one
+ * reference call: every statistic below is per group).  node_degree [n_nodes] f32 (TempME.node_degree),
+ * node6 [G,B,W,6] i32, ts3 [G,B,W,3] f32, cut [G,B] f64 -> out_wgt [G,B,W] f32:
+ *   diff = |float(cut[b]) - max_p ts3[b,w,p]|,  rec = exp(-diff / (std(diff) + 1e-6))          (:279-285)
+ *   avg  = sum_k [node6_k > 0] degree[node6_k] / (count_k [node6_k > 0] + 1e-6)                 (:289-295)
+ *   dw   = sigmoid((avg - mean(avg)) / (std(avg) + 1e-6)),  imp = 0.5 rec + 0.5 dw              (:298-301)
+ *   wgt  = imp / (sum_w imp / W + 1e-6)                                                         (:304)
+ * Elementwise arithmetic is fp32 with IEEE division; the two unbiased stds and the mean are fp64 sums of the
+ * fp32 elements in a fixed order, rounded to fp32 (deterministic; a group of one walk gives NaN, as torch.std).
+ * A node id outside [0, n_nodes) sets *err_flag (nullable device int32) to TM_E_ARG and counts as padding. */
+int tm_walk_importance(const float *node_degree, int32_t n_nodes, int32_t n_groups, int32_t B, int32_t W,
+                       const int32_t *node6, const float *ts3, const double *cut, float *out_wgt, int32_t *err_flag,
+                       void *stream);
+
+/* Workspace bytes tm_encoder_pool_fwd needs for n_walks walks. */
+int64_t tm_encoder_pool_workspace_bytes(const tm_weights *w, int64_t n_walks);
+
+/* enhance_predict_walks (explainer_new.py:221-258), eval, for n_groups groups: the inputs of
+ * tm_encoder_fwd_tab (etab nullable) plus the walk weights wgt [G,B,W] (tm_walk_importance) ->
+ *   out[(g B + b) ld_out + 0 .. h)       = sum_w wgt[g,b,w] * attention(...)[g,b,w,:]            (:241-252)
+ *   out[(g B + b) ld_out + h .. h + 12)  = sum_w onehot(cat[g,b,w]) with the category feature    (:254-256)
+ * (h = the hid_dim of tm_weights_create_ex; ld_out >= h (+ 12) floats, so the rows may sit in a wider buffer
+ * such as [G, B, node_emd_dim] whose last columns hold the base model's embedding).  The walk kernels end at
+ * attention.MLP's relu'd hidden layer h_w: its last Linear commutes with the weighted sum over walks
+ * (sum_w wgt_w (A2 h_w + b2) = A2 sum_w wgt_w h_w + b2 sum_w wgt_w) and runs once per event, and the three
+ * products of the scoring MLP (:195-200) are not executed.  Partials are summed in a fixed order, no float
+ * atomics: bitwise reproducible.  Covers every variant tm_encoder_fwd_tab covers (the fused kernel for
+ * hid_dim 64 with the category feature, table / zero-node / M > 1 forms included; the LDS-tiled kernels
+ * otherwise).  Replaces the encoder half of enhance_main.py:179 / :350. */
+int tm_encoder_pool_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
+                        int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6, const int32_t *eid3,
+                        const float *ts3, const int32_t *cat, const double *cut, const float *cnt, const float *wgt,
+                        void *workspace, float *out, int64_t ld_out, void *stream);
+
 /* ---------------------------------------------------------------- encoder training (device)
  * Training forward of TempME.forward (explainer_new.py:174-201) with dropout active: drop (nullable
  * = eval) holds uint8 keep-masks [n_walks][DC], DC = (2 + h + hm) rounded up to 16 (144 for the

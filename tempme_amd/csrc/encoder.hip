@@ -242,12 +242,15 @@ __global__ void __launch_bounds__(256) gcn_kernel(EncW P, int64_t n_rows, const 
 
 // ------------------------------------------------------------------ attention head + final MLP: TR walks per block
 // TR = 32, or 16 where the 32-walk tiles exceed the LDS (hid_dim above 152)
-template <int TR>
+// POOL (tm_encoder_pool_fwd): the kernel ends at attention.MLP's hidden layer and writes out[walk][h] =
+// wgt[walk] * relu(attention.MLP.0 O) (zero in the padded columns) for pool_tail_kernel to sum per event
+template <int TR, bool POOL = false>
 __global__ void __launch_bounds__(256) head_kernel(EncW P, int64_t n_walks, int64_t walks_per_group, int32_t W,
                                                    const float *__restrict__ F, const float *__restrict__ ts3,
                                                    const double *__restrict__ cut, const int32_t *__restrict__ cat,
                                                    const float *__restrict__ stdv, float *__restrict__ out,
-                                                   const uint8_t *__restrict__ drop = nullptr, float dscale = 1.f) {
+                                                   const uint8_t *__restrict__ drop = nullptr, float dscale = 1.f,
+                                                   const float *__restrict__ wgt = nullptr) {
     // drop (training forward, nullable): keep-masks [n_walks][DROP_COLS]; kept values are scaled by dscale
     static_assert(TR == 32 || TR == 16, "head_kernel: 16 or 32 walks per workgroup");
     constexpr int MT1 = TR / 16, MT2 = TR / 8;   // row tiles of TR and 2 TR rows
@@ -339,6 +342,16 @@ __global__ void __launch_bounds__(256) head_kernel(EncW P, int64_t n_walks, int6
         Pp[w * LD + c] = S[w * LD + c] + o;
     }
     __syncthreads();
+    if constexpr (POOL) {
+        gemm<MT1>(Pp, LD, P.a1, [&](int mt, int nt, floatx4 acc) {
+            const int c = ecol(nt);
+            for (int r = 0; r < 4; ++r) {
+                const int64_t gw = w0 + erow(mt, r);
+                if (gw < n_walks) out[gw * h + c] = wgt[gw] * relu(acc[r] + P.a1.b[c]);
+            }
+        });
+        return;
+    }
     gemm<MT1>(Pp, LD, P.a1, [&](int mt, int nt, floatx4 acc) {
         const int c = ecol(nt);
         for (int r = 0; r < 4; ++r) {
@@ -831,6 +844,9 @@ struct WalkArgs {
     float *out;
     const float *etab;    // [n_ids][16*NTD] lin_event's edge-feature part + bias per edge id (Q0 > 0)
     uint32_t *ticket;     // the launch's unit counter (persistent waves; zeroed before the launch)
+    // POOL instances (tm_encoder_pool_fwd): the walk weights [n_walks]; `out` is then the slot partials
+    // [n_slots * PM][HID] (PM = M in the split form, else 1) that pool_tail_kernel sums
+    const float *wgt = nullptr;
 };
 
 // Phase timing (debug builds only, -DTM_STAMPS; tools/stamps.py): s_memtime deltas of lane 0 per
@@ -1260,6 +1276,7 @@ struct HeadIn {
     float sd, t0, t1;
     int32_t c;
     bool v;
+    float wt;             // POOL instances: the walk's importance weight (a.wgt)
 };
 
 // per-wave LDS stash of a slot's position-2 results, read by its walks' position-0/1 passes
@@ -1336,6 +1353,47 @@ __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsr
     if (valid && g == 0) a.out[gw] = 1.f / (1.f + expf(-z));
 }
 
+// POOL ending of a walk (enhance_predict_walks, explainer_new.py:241-252): walk_head up to attention.MLP's
+// relu'd hidden layer h_w = relu(P2 + A1G (alpha_0 H_0 + alpha_1 H_1)), then acc += wgt_w h_w.  The layer's last
+// Linear commutes with the weighted sum over walks (sum_w wgt_w (A2 h_w + b2) = A2 sum_w wgt_w h_w + b2 sum_w wgt_w):
+// pool_tail_kernel applies it once per event, and the M1A2 / M2 / M3 products of the scoring MLP are not executed.
+// A1G's last refills load nx_end (the next pass's lin_event fragments).
+template <int NQE, int NTD, bool ZN, int NA>
+__device__ __forceinline__ void walk_pool_head(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, bool valid, const HeadIn &hi,
+                                               const Stash &st, float s0, float s1, const floatx4 (&H0)[NA],
+                                               const floatx4 (&H1)[NA], float4 (&pre)[PFP], const NextFr &nx_end,
+                                               floatx4 (&acc)[4]) {
+    static_assert(NA == (ZN ? 4 : 8), "U_i (zero-node form) or H_i");
+    const EncW &P = a.P;
+    const int lane = threadIdx.x & 63;
+    float tw0 = 1.f, tw1 = 1.f;
+    if (valid && P.tg) {
+        const float cu = hi.v ? (float)hi.cu : 0.f, sd = hi.v ? hi.sd + 1e-6f : 1.f;
+        tw0 = expf(-fabsf(cu - (hi.v ? hi.t0 : 0.f)) / sd);
+        tw1 = expf(-fabsf(cu - (hi.v ? hi.t1 : 0.f)) / sd);
+    }
+    s0 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw0));
+    s1 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw1));
+    const float mx = fmaxf(s0, s1), e0 = expf(s0 - mx), e1 = expf(s1 - mx), sum = e0 + e1;
+    const float al0 = e0 / sum, al1 = e1 / sum;
+    floatx4 Hm[NA];
+#pragma unroll
+    for (int t = 0; t < NA; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Hm[t][r] = al0 * H0[t][r] + al1 * H1[t][r];
+    }
+    floatx4 X[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) X[t] = st.P2[t][lane];
+    cgemm_p<4, NA, NA, ZN ? FoldLay::A1GZ : FoldLay::A1G>(wr, Hm, X, pre, nx_end);
+    const float wt = (valid && hi.v) ? hi.wt : 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[t][r] = __builtin_fmaf(wt, relu(X[t][r]), acc[t][r]);
+    }
+}
+
 // this column's V . H (the 4 lane groups' parts summed); ZN: VZ . U over the first 4 tiles
 template <bool ZN = false>
 __device__ __forceinline__ float score_dot(const Stash &st, const floatx4 (&H)[8]) {
@@ -1357,7 +1415,10 @@ __device__ __forceinline__ float score_dot(const Stash &st, const floatx4 (&H)[8
 // (Running the three positions of an M == 1 unit on three waves at once, the stash and position 0's inputs
 // crossing LDS behind workgroup barriers, measured no faster for the drop-in: with three side calls in flight
 // the 3x waves no longer fit one round of residency -- profiles/r05_dropin_pp_ab.txt.)
-template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false>
+// POOL (tm_encoder_pool_fwd): a walk ends at attention.MLP's hidden layer (walk_pool_head); a slot's M weighted
+// hidden vectors are summed in registers and written as one partial per slot (SPLIT: one per walk, each wave
+// holding one walk of the slot) at a.out.
+template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false, bool POOL = false>
 __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk_kernel(WalkArgs a) {
     using C = WalkConsts<NQE, NTD>;
     constexpr int NA = ZN ? 4 : 8;                      // tiles of a position's hidden vector (ZN: U alone)
@@ -1422,6 +1483,11 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     // position-0 pass overwrites both, so no unit reads another's
     floatx4 H0[NA];
     float s0 = 0.f;
+    floatx4 PA[POOL ? 4 : 1];                           // POOL: sum of wgt_w h_w over the slot's walks so far
+    if constexpr (POOL) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) PA[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+    }
     const int n_pass = SPLIT ? 3 : 1 + 2 * a.M;
     PosIn cur = load_pos(a, eg * a.W + (int64_t)j * a.M, 2, valid);
     float ef[EQ_MAX][4] = {};
@@ -1480,6 +1546,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             hi.t0 = a.ts3[gw * 3 + 0];
             hi.t1 = a.ts3[gw * 3 + 1];
             hi.c = a.cat[gw];
+            if constexpr (POOL) hi.wt = a.wgt[gw];
         };
         // next pass's scalars (after the last pass: the next unit's slot pass); its edge features / table
         // row once this pass's lin_event is done
@@ -1578,7 +1645,22 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             for (int t = 0; t < NA; ++t) H0[t] = H[t];
             s0 = s;
         }
-        if (p == 1) {
+        if constexpr (POOL) {
+            if (p == 1) {
+                if constexpr (ZN) walk_pool_head<NQE, NTD, ZN>(a, wr, valid, hi, st, s0, s, H0, Uv, pre, lin0, PA);
+                else walk_pool_head<NQE, NTD, ZN>(a, wr, valid, hi, st, s0, s, H0, H, pre, lin0, PA);
+                if (SPLIT || m + 1 == a.M) {                // the slot's last walk: its partial, one row of HID
+                    const int64_t row = SPLIT ? (unit * 16 + col) * a.M + m0 : unit * 16 + col;
+                    float *dst = a.out + row * HID + 4 * (lane >> 4);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        if (valid)
+                            *reinterpret_cast<float4 *>(dst + 16 * t) = make_float4(PA[t][0], PA[t][1], PA[t][2], PA[t][3]);
+                        PA[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+                    }
+                }
+            }
+        } else if (p == 1) {
             if constexpr (ZN) walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, Uv, pre, lin0);
             else walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, H, pre, lin0);
         }
@@ -2200,12 +2282,12 @@ constexpr int64_t WALK_SPLIT_UNITS = 512;
 static bool walk_split(int64_t units, int32_t M) { return units * M <= 3 * WALK_SPLIT_UNITS && units < WALK_SPLIT_UNITS; }
 
 // a.ticket zeroed on the stream before the launch unless walk_split (encoder_fwd_impl)
-template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false>
+template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false, bool POOL = false>
 static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     const int64_t units = (a.n_slots + 15) / 16;
     if (walk_split(units, a.M)) {
         const unsigned sb = (unsigned)((units * a.M + WALK_WPB - 1) / WALK_WPB);
-        walk_kernel<NQE, 11, SEF, Q0, true, ZN><<<dim3(sb), 64 * WALK_WPB, 0, s>>>(a);
+        walk_kernel<NQE, 11, SEF, Q0, true, ZN, POOL><<<dim3(sb), 64 * WALK_WPB, 0, s>>>(a);
         return;
     }
     // one round of resident workgroups (occupancy x CUs of the current device), cached per instance
@@ -2214,7 +2296,7 @@ static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
         if (cap[dev] == 0) {
             int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN>, 64 * WALK_WPB, 0) ==
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL>, 64 * WALK_WPB, 0) ==
                     hipSuccess &&
                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0 &&
                 cus > 0)
@@ -2226,7 +2308,7 @@ static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     }
     const int dbg = debug_opt(TM_DEBUG_WALK_BLOCKS);   // A/B of smaller persistent grids (tools/walk_grid_ab.sh)
     if (dbg > 0 && blocks > (unsigned)dbg) blocks = (unsigned)dbg;
-    walk_kernel<NQE, 11, SEF, Q0, false, ZN><<<dim3(blocks), 64 * WALK_WPB, 0, s>>>(a);
+    walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL><<<dim3(blocks), 64 * WALK_WPB, 0, s>>>(a);
 }
 
 extern "C" int tm_encoder_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
@@ -2324,6 +2406,104 @@ static int encoder_fwd_impl(const tm_weights *w, const float *n_feat, const floa
     launch_head(P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, out_imp, nullptr, 1.f, s);
     TM_CHECK_LAUNCH();
     prof_end("head_kernel", s, pe);
+    return TM_OK;
+}
+
+// ------------------------------------------------------------------ pooled encoder (enhance_predict_walks)
+// the workspace of tm_encoder_pool_fwd: tm_encoder_fwd's (F, the groups' std, the unit counter), then the
+// partials [n_walks][h] (the fused kernel uses n_slots * PM <= n_walks rows of them)
+static int64_t pool_part_offset(const tm_weights *w, int64_t n_walks) {
+    return (tm_encoder_workspace_bytes(w, n_walks) + 255) & ~(int64_t)255;
+}
+
+extern "C" int64_t tm_encoder_pool_workspace_bytes(const tm_weights *w, int64_t n_walks) {
+    return pool_part_offset(w, n_walks) + n_walks * (w ? w->h : HID) * (int64_t)sizeof(float) + 256;
+}
+
+// the fused kernel's POOL instance for these dims (the instance table of encoder_fwd_impl)
+static void launch_walk_pool(const WalkArgs &a, int nqe, bool wide, int q0, int node_zero, unsigned blocks,
+                             hipStream_t s) {
+    if (q0 == 2 && node_zero) {
+        if (nqe == 11) launch_walk<11, false, 2, true, true>(a, blocks, s);
+        else if (nqe == 12) launch_walk<12, false, 2, true, true>(a, blocks, s);
+        else if (nqe == 13) launch_walk<13, false, 2, true, true>(a, blocks, s);
+        else launch_walk<14, false, 2, true, true>(a, blocks, s);
+    } else if (q0 == 2) {
+        if (nqe == 11) launch_walk<11, false, 2, false, true>(a, blocks, s);
+        else if (nqe == 12) launch_walk<12, false, 2, false, true>(a, blocks, s);
+        else if (nqe == 13) launch_walk<13, false, 2, false, true>(a, blocks, s);
+        else launch_walk<14, false, 2, false, true>(a, blocks, s);
+    } else if (q0 == 10) {
+        if (nqe == 21) launch_walk<21, false, 10, false, true>(a, blocks, s);
+        else launch_walk<22, false, 10, false, true>(a, blocks, s);
+    } else if (wide) {
+        if (nqe == 21) launch_walk<21, true, 0, false, true>(a, blocks, s);
+        else launch_walk<22, true, 0, false, true>(a, blocks, s);
+    } else if (nqe == 11) launch_walk<11, false, 0, false, true>(a, blocks, s);
+    else if (nqe == 12) launch_walk<12, false, 0, false, true>(a, blocks, s);
+    else if (nqe == 13) launch_walk<13, false, 0, false, true>(a, blocks, s);
+    else launch_walk<14, false, 0, false, true>(a, blocks, s);
+}
+
+extern "C" int tm_encoder_pool_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
+                                   int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6,
+                                   const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
+                                   const float *cnt, const float *wgt, void *workspace, float *out, int64_t ld_out,
+                                   void *stream) {
+    if (!w || n_groups < 0 || B < 0 || W < 0 || M <= 0) return fail(TM_E_ARG, "tm_encoder_pool_fwd: bad arguments");
+    if (W % M) return fail(TM_E_SHAPE, "tm_encoder_pool_fwd: W must be a multiple of M (walks per hop-1 slot)");
+    const int64_t n_walks = (int64_t)n_groups * B * W, n_events = (int64_t)n_groups * B;
+    if (n_events == 0) return TM_OK;
+    const EncW &P = w->P;
+    if (ld_out < P.hm) return fail(TM_E_ARG, "tm_encoder_pool_fwd: ld_out below the row width (hid_dim (+ 12))");
+    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !out)
+        return fail(TM_E_ARG, "tm_encoder_pool_fwd: NULL pointer");
+    const size_t lds_g = gcn_lds(P);
+    if (lds_g > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: feature dims too large for LDS tile");
+    hipStream_t s = S_(stream);
+    float *F = reinterpret_cast<float *>(workspace);
+    float *stdv = F + n_walks * 3 * 2 * P.h;
+    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + pool_part_offset(w, n_walks));
+    int32_t n_part = W;                                   // partial rows per event
+    if (n_walks > 0) {
+        hipEvent_t pe = prof_begin(s);
+        if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
+        TM_CHECK_LAUNCH();
+        prof_end("std_kernel", s, pe);
+        if (etab && etab_q0(P) == 0) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: no edge table for these dims");
+        const int nqe = r16(P.kev) / 16, ntd = r16(P.dn) / 16;
+        const bool narrow = nqe >= 11 && nqe <= 14 && P.de <= 16 * EQ_MAX;
+        const bool wide = (nqe == 21 || nqe == 22) && P.de > 16 * EQ_MAX && P.de % 4 == 0;
+        if (ntd == 11 && P.dn % 4 == 0 && (narrow || wide) && P.h == HID && P.cat) {
+            if (!walk_layout_ok(P, nqe)) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: weight layout mismatch");
+            const int64_t n_slots = n_walks / M;
+            const int64_t units = (n_slots + 15) / 16;
+            WalkArgs a{P, n_slots, W, M, B * W, n_feat, e_feat, node6, eid3, cat, ts3, cnt, stdv, cut, part, etab,
+                       reinterpret_cast<uint32_t *>(F), wgt};
+            const unsigned blocks = (unsigned)((units + WALK_WPB - 1) / WALK_WPB);
+            const bool split = walk_split(units, M);
+            if (!split) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
+            n_part = split ? W : W / M;
+            pe = prof_begin(s);
+            launch_walk_pool(a, nqe, wide, etab ? etab_q0(P) : 0, w->node_zero, blocks, s);
+            TM_CHECK_LAUNCH();
+            prof_end("walk_pool_kernel", s, pe);
+        } else {
+            pe = prof_begin(s);
+            launch_gcn(P, w->node_zero, n_walks * 3, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
+            TM_CHECK_LAUNCH();
+            prof_end("gcn_kernel", s, pe);
+            pe = prof_begin(s);
+            head_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, head_lds(P, 16), s>>>(
+                P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, part, nullptr, 1.f, wgt);
+            TM_CHECK_LAUNCH();
+            prof_end("head_pool_kernel", s, pe);
+        }
+    }
+    hipEvent_t pe = prof_begin(s);
+    launch_pool_tail(P.a2, n_events, W, n_part, P.h, P.cat, part, wgt, cat, out, ld_out, s);
+    TM_CHECK_LAUNCH();
+    prof_end("pool_tail_kernel", s, pe);
     return TM_OK;
 }
 

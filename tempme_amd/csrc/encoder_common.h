@@ -258,6 +258,13 @@ __device__ __forceinline__ void rgemm(const Lin &L, const floatx4 (&x)[NQ], floa
 bool launch_gcn_fwd_reg(const EncW &P, int node_zero, int64_t n_rows, const float *n_feat, const float *e_feat, const int32_t *node6,
                         const int32_t *eid3, const float *ts3, const float *cnt, float *F, hipStream_t s);
 
+// enhance.hip: the pooled encoder's tail, one workgroup per (group, event): out[e][0:h] = a2 (sum of the event's
+// n_part partial rows of `part`, in a fixed order) + a2.b * (sum of its W walk weights, in order), and with do_cat
+// out[e][h:h+12] = the event's category histogram
+void launch_pool_tail(const Lin &a2, int64_t n_events, int32_t W, int32_t n_part, int32_t h, int32_t do_cat,
+                      const float *part, const float *wgt, const int32_t *cat, float *out, int64_t ld_out,
+                      hipStream_t s);
+
 }  // namespace tmk
 
 using tmk::Lin;

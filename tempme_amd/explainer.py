@@ -88,6 +88,10 @@ class _MergeLayer(nn.Module):
         nn.init.xavier_normal_(self.fc2.weight)
         self.act = nn.ReLU()
 
+    def forward(self, x1, x2):
+        """explainer_new.py:71-76."""
+        return self.fc2(self.act(self.fc1(torch.cat([x1, x2], dim=-1))))
+
 
 class event_gcn(nn.Module):  # noqa: N801  (reference name, kept for state_dict keys)
     def __init__(self, event_dim, node_dim, hid_dim):
@@ -213,6 +217,28 @@ def _to_many(device, *items):
     if device.type == "cuda" and all(isinstance(a, np.ndarray) and d in _NP for a, d in items):
         return _STAGE(device, items)
     return [_to(a, device, d).contiguous() for a, d in items]
+
+
+def compute_node_degrees(src, dst, num_nodes=None):
+    """compute_node_degrees.py:20-111 on an edge list: the undirected degree of every node id (an edge counts once
+    at each end, a self-loop twice), 1.0 for ids no edge touches, as a float32 tensor [max id + 1]; with
+    ``num_nodes`` padded with ones or truncated to that length (update_explainer_node_degrees, :95-108), which is
+    what ``TempME.set_node_degree`` expects."""
+    as_np = lambda a: (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).astype(np.int64).ravel()  # noqa: E731
+    src, dst = as_np(src), as_np(dst)
+    if src.shape != dst.shape:
+        raise ValueError("compute_node_degrees: src and dst differ in length")
+    if src.size and min(src.min(), dst.min()) < 0:
+        raise ValueError("compute_node_degrees: negative node id")
+    n = int(max(src.max(), dst.max())) + 1 if src.size else 0
+    cnt = np.bincount(src, minlength=n) + np.bincount(dst, minlength=n)
+    deg = np.where(cnt > 0, cnt, 1).astype(np.float32)
+    if num_nodes is not None:
+        out = np.ones(int(num_nodes), dtype=np.float32)
+        k = min(n, int(num_nodes))
+        out[:k] = deg[:k]
+        deg = out
+    return torch.from_numpy(deg)
 
 
 class TempME(nn.Module):
@@ -1197,6 +1223,190 @@ class TempME(nn.Module):
             return [torch.cat([s0, t0, b0], dim=0), torch.cat([s1, t1, b1], dim=0)]
         return [torch.cat([s0, t0, b0], dim=0)]
 
+    # ------------------------------------------------------------------ motif-enhanced link prediction
+    def set_node_degree(self, t):
+        """``node_degree`` (explainer_new.py:134-137; all ones until set) from a per-node-id tensor or array,
+        e.g. ``compute_node_degrees(src, dst, num_nodes)``: one entry per row of the node-feature table, moved to
+        the explainer's device as float32.  With the all-ones default the degree half of the walk weights is
+        rounding noise, so enhance_main.py's loops should call this once after construction."""
+        t = torch.as_tensor(t)
+        n = self.node_raw_embed.weight.shape[0]
+        if t.dim() != 1 or t.shape[0] != n:
+            raise ValueError("set_node_degree: expected %d entries (one per node-feature row), got shape %s"
+                             % (n, tuple(t.shape)))
+        dev = self.node_raw_embed.weight.device if self.device is None else self.device
+        self.node_degree = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        return self
+
+    def _degree_dev(self, dev):
+        """node_degree as a contiguous float32 tensor on dev (a plain attribute, as in the reference: Module.to
+        does not move it), converted once per (tensor, version)."""
+        d = self.node_degree
+        c = self.__dict__.get("_deg_c")
+        if c is None or c[0] is not d or c[1] != d._version or c[2].device != dev:
+            c = self.__dict__["_deg_c"] = (d, d._version, d.detach().to(device=dev, dtype=torch.float32).contiguous())
+        return c[2]
+
+    def walk_importance_groups(self, node6, ts3, cut, n_groups, B, W, check=True):
+        """compute_walk_importance for n_groups reference calls at once (tm_walk_importance): device tensors
+        node6 [G,B,W,6] int32, ts3 [G,B,W,3] f32, cut [G,B] f64 -> [G,B,W] f32.  check: read the kernel's
+        index-error flag (a host sync) and raise IndexError for a node id outside node_degree."""
+        dev = self._dev()
+        deg = self._degree_dev(dev)
+        out = torch.empty((n_groups, B, W), dtype=torch.float32, device=dev)
+        err = self.__dict__.get("_enh_err")
+        if err is None or err.device != dev:
+            err = self.__dict__["_enh_err"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        L.check(L.lib().tm_walk_importance(L.ptr(deg), int(deg.shape[0]), n_groups, B, W, L.ptr(node6), L.ptr(ts3),
+                                           L.ptr(cut), L.ptr(out), L.ptr(err), L.stream_ptr(dev)),
+                "compute_walk_importance")
+        if check:
+            code = int(err.item())
+            if code:
+                err.zero_()
+                L.raise_device_error(code, "compute_walk_importance")
+        return out
+
+    def enhance_groups(self, node6, eid3, ts3, cat, cut, cnt, n_groups, B, W, M=1, etab=None, out=None, check=True):
+        """enhance_predict_walks for n_groups independent reference calls at once (e.g. the src/tgt/bgd sides of
+        one batch), eval, no gradients: one tm_walk_importance and one tm_encoder_pool_fwd launch.  Inputs are
+        device tensors shaped [G,B,W,...] with forward_groups' dtypes (int32 node6 / eid3 / cat, f32 ts3 / cnt,
+        f64 cut); M and etab as in encoder_fwd.  Returns [G, B, hid_dim (+ 12)]; ``out``: a float32 [G, B, C]
+        buffer with C >= hid_dim (+ 12) whose leading columns are written instead (the rest is left as is)."""
+        dev = self._dev()
+        self._hip_eval_ok()
+        nt, et = self.feature_tables()
+        w = self.packed_weights()
+        wgt = self.walk_importance_groups(node6, ts3, cut, n_groups, B, W, check=check)
+        h, H = self.hid_dim, self._hid_packed()
+        cols = self.mlp_dim
+        direct = H == h and out is not None
+        if direct:
+            if out.dtype != torch.float32 or out.dim() != 3 or tuple(out.shape[:2]) != (n_groups, B) or \
+                    out.shape[2] < cols or not out.is_contiguous() or out.device != dev:
+                raise ValueError("enhance_groups: out must be a contiguous float32 [G, B, >= %d] tensor on %s"
+                                 % (cols, dev))
+            buf = out
+        else:
+            buf = torch.empty((n_groups, B, H + 12 if self.if_cat else H), dtype=torch.float32, device=dev)
+        n_walks = n_groups * B * W
+        ws = torch.empty(L.lib().tm_encoder_pool_workspace_bytes(w, n_walks), dtype=torch.uint8, device=dev)
+        L.check(L.lib().tm_encoder_pool_fwd(w, L.ptr(nt), L.ptr(et), None if etab is None else L.ptr(etab), n_groups, B,
+                                            W, M, L.ptr(node6), L.ptr(eid3), L.ptr(ts3), L.ptr(cat), L.ptr(cut),
+                                            L.ptr(cnt), L.ptr(wgt), L.ptr(ws), L.ptr(buf), int(buf.shape[2]),
+                                            L.stream_ptr(dev)), "enhance_predict_walks")
+        if direct:
+            return out[:, :, :cols]
+        if H != h:
+            buf = buf.index_select(2, self._pad_maps(dev)["cm"])    # [hidden units | histogram] of the padded row
+        if out is not None:
+            out[:, :, :cols] = buf
+            return out[:, :, :cols]
+        return buf
+
+    def _enhance_sides_eval(self, sides, cut_time_l):
+        """The eval path of enhance_predict_*: sides = [(walks, edge_identify), ...] of one batch (same B and W)
+        as G groups -> [G, B, node_emd_dim] whose leading hid_dim (+ 12) columns hold the walk embeddings."""
+        dev = self._dev()
+        G = len(sides)
+        B, W = np.shape(sides[0][0][1])[0], np.shape(sides[0][0][1])[1]
+        n_node, n_edge = self.node_raw_embed.weight.shape[0], self.edge_raw_embed.weight.shape[0]
+        host = all(isinstance(a, np.ndarray) for wk, ei in sides for a in (wk[0], wk[1], wk[2], wk[3], ei))
+        if host:
+            for wk, _ in sides:
+                # what the reference's embedding lookups raise; the kernels then never see an id outside the tables
+                for a, n in ((wk[1], n_edge), (wk[0], n_node)):
+                    if a.size and (a.max() >= n or a.min() < 0):
+                        raise IndexError("index out of range in self")
+            st = lambda k, shp: np.stack([np.asarray(s[0][k]).reshape(shp) for s in sides])  # noqa: E731
+            items = ((st(0, (B, W, 6)), torch.int32), (st(1, (B, W, 3)), torch.int32), (st(2, (B, W, 3)), torch.float32),
+                     (st(3, (B, W)), torch.int32), (np.asarray(cut_time_l, dtype=np.float64), torch.float64),
+                     (np.stack([np.asarray(s[1]).reshape(B, W, 3, 3) for s in sides]), torch.float32))
+            n6, e3, t3, ct, cu, ei = _to_many(dev, *items)
+        else:
+            st = lambda k, shp, dt: torch.stack([_to(s[0][k], dev, dt).reshape(shp) for s in sides])  # noqa: E731
+            n6, e3, t3 = st(0, (B, W, 6), torch.int32), st(1, (B, W, 3), torch.int32), st(2, (B, W, 3), torch.float32)
+            ct = st(3, (B, W), torch.int32)
+            cu = _to(cut_time_l, dev, torch.float64)
+            ei = torch.stack([_to(s[1], dev, torch.float32).reshape(B, W, 3, 3) for s in sides])
+        cu = cu.reshape(1, B).expand(G, B).contiguous()
+        emb = torch.empty((G, B, self.node_emd_dim), dtype=torch.float32, device=dev)
+        etab = self.dropin_edge_table()
+        if etab is not None and not host and int(e3.max()) >= etab.shape[0]:
+            raise IndexError("index out of range in self")
+        # host arrays were checked against the node table above; a shorter node_degree (assigned directly, as the
+        # reference allows) still goes through the kernel's own flag
+        self.enhance_groups(n6, e3, t3, ct, cu, ei, G, B, W, etab=etab, out=emb,
+                            check=not host or self.node_degree.shape[0] < n_node)
+        return emb
+
+    def compute_walk_importance(self, time_idx, node_idx, cut_time_l):
+        """explainer_new.py:260-306 -> [bsz, n_walk]: on a HIP device one tm_walk_importance launch (fp64 group
+        statistics), else the torch formulation."""
+        dev = self.node_raw_embed.weight.device if self.device is None else torch.device(self.device)
+        B, W = np.shape(time_idx)[0], np.shape(time_idx)[1]
+        if dev.type != "cuda":
+            return self._walk_importance_torch(_to(time_idx, dev, torch.float32), _to(node_idx, dev, torch.long),
+                                               _to(cut_time_l, dev, torch.float32))
+        dev = self._dev()
+        n6, t3, cu = _to_many(dev, (node_idx, torch.int32), (time_idx, torch.float32), (cut_time_l, torch.float64))
+        return self.walk_importance_groups(n6, t3, cu, 1, B, W)[0]
+
+    def _enhance_eval(self):
+        """The HIP eval path serves a module in eval mode on a HIP device when no gradient can be asked for:
+        grad mode off, or neither the encoder's nor affinity_score's parameters require one."""
+        dev = self.node_raw_embed.weight.device if self.device is None else torch.device(self.device)
+        if dev.type != "cuda" or self._needs_autograd():
+            return False
+        return not (torch.is_grad_enabled() and any(p.requires_grad for p in self.affinity_score.parameters()))
+
+    def enhance_predict_walks(self, walks, cut_time_l, edge_identify):
+        """explainer_new.py:221-258 -> [bsz, hid_dim (+ 12)]."""
+        if not self._enhance_eval():
+            return self._enhance_walks_torch(walks, cut_time_l, edge_identify)
+        return self._enhance_sides_eval([(walks, edge_identify)], cut_time_l)[0, :, :self.mlp_dim]
+
+    def enhance_predict_pairs(self, walks_src, walks_tgt, cut_time_l, src_edge, tgt_edge):
+        """explainer_new.py:215-218 -> two [bsz, hid_dim (+ 12)]; eval: both sides in one launch."""
+        if not self._enhance_eval() or np.shape(walks_src[1]) != np.shape(walks_tgt[1]):
+            return (self.enhance_predict_walks(walks_src, cut_time_l, src_edge),
+                    self.enhance_predict_walks(walks_tgt, cut_time_l, tgt_edge))
+        emb = self._enhance_sides_eval([(walks_src, src_edge), (walks_tgt, tgt_edge)], cut_time_l)
+        return emb[0, :, :self.mlp_dim], emb[1, :, :self.mlp_dim]
+
+    def enhance_predict_agg(self, ts_l_cut, walks_src, walks_tgt, walks_bgd, edge_id_info, src_gat, tgt_gat, bgd_gat):
+        """explainer_new.py:203-213 -> (pos_score, neg_score), each [bsz, 1].  Eval without gradients: the three
+        sides are three groups of one walk-importance and one pooled-encoder launch (the reference encodes
+        walks_src twice with identical results, :205 / :209; here once), written into one [3, B, node_emd_dim]
+        buffer beside the base embeddings; affinity_score runs in torch ops with fc1's src half computed once for
+        the positive and the negative pair.  Training, or gradients wanted: the torch formulation, with the
+        reference's two src encodings (dropout draws as the reference does)."""
+        src_edge, tgt_edge, bgd_edge = edge_id_info
+        gat_grad = torch.is_grad_enabled() and any(g.requires_grad for g in (src_gat, tgt_gat, bgd_gat))
+        if not self._enhance_eval():
+            return self._enhance_agg_torch(ts_l_cut, ((walks_src, src_edge), (walks_tgt, tgt_edge), (walks_bgd, bgd_edge)),
+                                           (src_gat, tgt_gat, bgd_gat))
+        if gat_grad or not (np.shape(walks_src[1]) == np.shape(walks_tgt[1]) == np.shape(walks_bgd[1])):
+            # frozen encoder, gradients to the base embeddings (or sides of different shapes): HIP embeddings per
+            # side, affinity_score through autograd
+            aff = self.affinity_score
+            s = self.enhance_predict_walks(walks_src, ts_l_cut, src_edge)
+            t = self.enhance_predict_walks(walks_tgt, ts_l_cut, tgt_edge)
+            b = self.enhance_predict_walks(walks_bgd, ts_l_cut, bgd_edge)
+            src_full = torch.cat([s, src_gat.to(s.device)], dim=-1)
+            return (aff(src_full, torch.cat([t, tgt_gat.to(s.device)], dim=-1)),
+                    aff(src_full, torch.cat([b, bgd_gat.to(s.device)], dim=-1)))
+        emb = self._enhance_sides_eval([(walks_src, src_edge), (walks_tgt, tgt_edge), (walks_bgd, bgd_edge)], ts_l_cut)
+        c, B, D = self.mlp_dim, emb.shape[1], self.node_emd_dim
+        for k, gat in enumerate((src_gat, tgt_gat, bgd_gat)):
+            emb[k, :, c:] = gat.detach()
+        fc1, fc2 = self.affinity_score.fc1, self.affinity_score.fc2
+        with torch.no_grad():
+            hs = F.linear(emb[0], fc1.weight[:, :D], fc1.bias)                      # [B, D], shared by pos and neg
+            ho = F.linear(emb[1:].reshape(2 * B, D), fc1.weight[:, D:])             # [2B, D]: tgt rows, then bgd rows
+            z = fc2(torch.relu(ho.view(2, B, D) + hs.unsqueeze(0)))
+        return z[0], z[1]
+
     def _fused_beta(self):
         """beta_sample(p, True) * mask may go through _BetaRsampleFn (bitwise the same as torch's Beta rsample):
         not when the module's beta_sample is overridden (an instance attribute or a subclass)."""
@@ -1263,6 +1473,16 @@ class TempME(nn.Module):
 
     # ------------------------------------------------------------------ autograd formulation (training)
     def _forward_torch(self, walks, cut_time_l, edge_identify):
+        out, _, _, dev = self._attention_torch(walks, cut_time_l, edge_identify)
+        B, W = out.shape[0], out.shape[1]
+        if self.if_cat:
+            oh = F.one_hot(_to(walks[3], dev, torch.long).reshape(B, W), num_classes=12)
+            out = torch.cat([out, oh.to(out.dtype)], dim=-1)
+        return self.MLP(out).sigmoid()
+
+    def _attention_torch(self, walks, cut_time_l, edge_identify):
+        """The encoder up to ``self.attention(...)`` (explainer_new.py:175-193 = :222-245) in torch ops:
+        -> (attention output [B, W, h], walk times f32 [B, W, 3], node ids long [B, W, 6], device)."""
         node_idx, edge_idx, time_idx, cat_feat, _ = walks
         dev = self.node_raw_embed.weight.device if self.device is None else self.device
         eid = _to(edge_idx, dev, torch.long)
@@ -1276,8 +1496,12 @@ class TempME(nn.Module):
         node = _to(node_idx, dev, torch.long)
         xs = self.node_raw_embed(node[:, :, [0, 2, 4]])
         xt = self.node_raw_embed(node[:, :, [1, 3, 5]])
-        us = self.event_conv(ev, xs, xt)
-        ut = self.event_conv(ev, xt, xs)
+        # event_gcn.forward for both branches (explainer_new.py:93-96) with lin_event applied once: the two calls
+        # compute the same product (bit-identical values), and its weight gradient then is one reduction
+        conv = self.event_conv
+        lev = _LinEventFn.apply(ev, conv.lin_event.weight, conv.lin_event.bias)
+        us = conv.MLP(xs + conv.relu(xt + lev))
+        ut = conv.MLP(xt + conv.relu(xs + lev))
         f = torch.cat([us, ut], dim=-1)
         at = self.attention
         src = f[:, :, 2, :]
@@ -1291,11 +1515,44 @@ class TempME(nn.Module):
         alpha = torch.softmax(scores, dim=-1)
         if isinstance(at, TemporalAwareAttention):
             alpha = at.dropout(alpha)
-        out = at.MLP(src + (alpha.unsqueeze(-1) * wq).sum(2))
+        return at.MLP(src + (alpha.unsqueeze(-1) * wq).sum(2)), t, node, dev
+
+    def _walk_importance_torch(self, t, node, cut):
+        """compute_walk_importance (explainer_new.py:275-306) in torch ops on the tensors' device: t [B, W, 3]
+        f32, node [B, W, 6] long, cut [B] f32 -> [B, W]."""
+        W = t.shape[1]
+        diff = torch.abs(cut.unsqueeze(1) - t.max(dim=-1)[0])
+        rec = torch.exp(-diff / (diff.std() + 1e-6))
+        valid = node > 0
+        deg = torch.where(valid, self.node_degree.to(node.device)[node].float(), torch.zeros_like(node, dtype=torch.float))
+        avg = deg.sum(dim=-1) / (valid.sum(dim=-1).float() + 1e-6)
+        dw = torch.sigmoid((avg - avg.mean()) / (avg.std() + 1e-6))
+        imp = 0.5 * rec + 0.5 * dw
+        return imp / (imp.sum(dim=-1, keepdim=True) / W + 1e-6)
+
+    def _enhance_walks_torch(self, walks, cut_time_l, edge_identify):
+        """enhance_predict_walks (explainer_new.py:221-258) in torch ops (training, or gradients wanted)."""
+        out, t, node, dev = self._attention_torch(walks, cut_time_l, edge_identify)
+        wgt = self._walk_importance_torch(t, node, _to(cut_time_l, dev, torch.float32))
+        x = (out * wgt.unsqueeze(-1)).sum(1)
         if self.if_cat:
-            oh = F.one_hot(_to(cat_feat, dev, torch.long).reshape(B, W), num_classes=12)
-            out = torch.cat([out, oh.to(out.dtype)], dim=-1)
-        return self.MLP(out).sigmoid()
+            B, W = out.shape[0], out.shape[1]
+            hist = F.one_hot(_to(walks[3], dev, torch.long).reshape(B, W), num_classes=12).sum(1)
+            x = torch.cat([x, hist.to(x.dtype)], dim=-1)
+        return x
+
+    def _enhance_agg_torch(self, ts_l_cut, sides, gats):
+        """enhance_predict_agg (explainer_new.py:203-213) in torch ops, in the reference's own sequence: two pair
+        calls, so walks_src is encoded twice and every dropout draws as it does there.  sides = three
+        (walks, edge_identify), gats = the three base embeddings."""
+        (w_s, e_s), (w_t, e_t), (w_b, e_b) = sides
+        enc, aff = self._enhance_walks_torch, self.affinity_score
+        s, t = enc(w_s, ts_l_cut, e_s), enc(w_t, ts_l_cut, e_t)
+        g_s, g_t, g_b = (g.to(s.device) for g in gats)
+        pos = aff(torch.cat([s, g_s], dim=-1), torch.cat([t, g_t], dim=-1))
+        s, b = enc(w_s, ts_l_cut, e_s), enc(w_b, ts_l_cut, e_b)
+        neg = aff(torch.cat([s, g_s], dim=-1), torch.cat([b, g_b], dim=-1))
+        return pos, neg
 
     def _edge_imp_torch(self, subgraph, graphlet_imp, walks, training):
         node_record, eidx_record, _ = subgraph
@@ -1329,6 +1586,30 @@ class _Packed:
         if self.h is not None and L._lib is not None:
             L._lib.tm_weights_free(self.h)
             self.h = None
+
+
+class _LinEventFn(torch.autograd.Function):
+    """event_conv.lin_event of the torch-op formulation: F.linear forward (the same values), with the weight and
+    bias gradients accumulated in fp64 and rounded once.  dW = dY^T X sums over every walk position of the call
+    (3 B W rows), and X is raw edge features, edge counts and cosines rather than O(1) activations, so the sum
+    cancels heavily; the device library's fp32 GEMM leaves ~4e-6 of the largest entry there (16x the CPU library's
+    error on the same product), which the fp64 accumulation removes.  Also makes this gradient
+    independent of the library's reduction order."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        return F.linear(x, w, b)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, w = ctx.saved_tensors
+        g2, x2 = g.reshape(-1, g.shape[-1]), x.reshape(-1, x.shape[-1])
+        dx = g.matmul(w) if ctx.needs_input_grad[0] else None
+        dw = g2.double().t().matmul(x2.double()).to(w.dtype) if ctx.needs_input_grad[1] else None
+        db = g2.double().sum(0).to(w.dtype) if ctx.needs_input_grad[2] else None
+        return dx, dw, db
 
 
 class _EncoderFn(torch.autograd.Function):

@@ -193,6 +193,13 @@ int tm_weights_set_node_zero(tm_weights *w, int32_t node_zero);
  * even of two objects allocated at the same address.  Caches of per-edge-id tables (tm_edge_tables) key on it. */
 uint64_t tm_weights_version(const tm_weights *w);
 int tm_weights_free(tm_weights *w);
+/* The exact three-way bf16 split the walk kernel's lin_event pack is built with (host function; no device
+ * needed): in[i] = hi[i] + mid[i] + lo[i] with each part a bf16 bit pattern (round to nearest even of the
+ * running residual), exactly for every finite |in[i]| >= 2^-110.  The high part never rounds a finite value
+ * to +-inf (the largest values truncate); below 2^-110 the residual parts fall under bf16's smallest denormal
+ * step 2^-133 and are rounded to it, so the sum is then within 2^-134 of the input.  A non-finite input goes
+ * through as its high part alone (mid = lo = 0). */
+void tm_weight_split3(const float *in, int64_t n, uint16_t *hi, uint16_t *mid, uint16_t *lo);
 
 /* Workspace bytes tm_encoder_fwd needs for n_walks walks. */
 int64_t tm_encoder_workspace_bytes(const tm_weights *w, int64_t n_walks);

@@ -174,6 +174,122 @@ static void run(const char *name, const void *w, float *out, int blocks, int ite
     printf("%-18s lds=%6d  %.3f ms  %.1f TFLOP/s (fp32-equivalent)\n", name, lds, ms, flop / ms / 1e9);
 }
 
+// ---- lin_event-shaped case: K = 192 generated features cos(dt w + phi) (fp64 range reduction + v_cos_f32, as
+// walk_kernel's cos_rd), 11 output tiles, weight fragments streamed from L2, the next K step's features
+// generated between this step's MFMAs.  MODE 0: v_mfma_f32_16x16x4_f32, 12 K steps of 16 (4 features per lane
+// per step); MODE 6: v_mfma_f32_16x16x32_bf16, 6 K steps of 32 (8 features per lane per step, split in
+// registers), six products per (tile, step), tile pairs interleaved.
+__device__ __forceinline__ float cos_feat(float dt, int k) {
+    const float x = dt * (1.0f / (float)(1 + k)) + 0.01f * (float)k;
+    const double u = (double)x * 0.15915494309189533577;
+    return __builtin_amdgcn_cosf((float)(u - __builtin_rint(u)));
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256, 2) lin_ev(const void *w, int iters, float *out) {
+    constexpr int NT = 11;
+    const int g = lane_id() >> 4;
+    floatx4 L[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) L[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma nounroll
+    for (int it = 0; it < iters; ++it) {
+        const float dt = 1e3f * (float)(it + 1) + (float)(threadIdx.x & 15);
+        if constexpr (MODE == 0) {
+            const float4 *wp = reinterpret_cast<const float4 *>(w) + lane_id();
+            constexpr int NQ = 12, N = NT * NQ, D = 4;
+            float4 buf[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) buf[i] = wp[((i % NT) * NQ + i / NT) * 64];
+            floatx4 xq;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) xq[s] = cos_feat(dt, 4 * g + s);
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                floatx4 xn = xq;
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const int i = q * NT + t;
+                    const float4 a = buf[i % D];
+                    if (i + D < N) buf[i % D] = wp[(((i + D) % NT) * NQ + (i + D) / NT) * 64];
+                    L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, xq.x, L[t], 0, 0, 0);
+                    L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, xq.y, L[t], 0, 0, 0);
+                    L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, xq.z, L[t], 0, 0, 0);
+                    L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, xq.w, L[t], 0, 0, 0);
+                    if (q + 1 < NQ && t < 4) xn[t] = cos_feat(dt, 16 * (q + 1) + 4 * g + t);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                xq = xn;
+            }
+        } else {
+            const bf16x8 *wp = reinterpret_cast<const bf16x8 *>(w) + lane_id();
+            constexpr int NS = 6, N = NT * NS * 3, D = 12;
+            auto off = [](int i) { return ((((i / 3) % NT) * NS + i / (3 * NT)) * 3 + i % 3) * 64; };
+            bf16x8 buf[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) buf[i] = wp[off(i)];
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = cos_feat(dt, 8 * g + j);
+            Split3 xs = split8(v);
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                float vn[8] = {};
+                auto take = [&](int i) {
+                    const bf16x8 a = buf[i % D];
+                    if (i + D < N) buf[i % D] = wp[off(i + D)];
+                    return a;
+                };
+#pragma unroll
+                for (int t = 0; t < NT; t += 2) {
+                    const int i = (s * NT + t) * 3;
+                    const bool two = t + 1 < NT;
+                    const bf16x8 h0 = take(i), m0 = take(i + 1), l0 = take(i + 2);
+                    bf16x8 h1 = h0, m1 = m0, l1 = l0;
+                    if (two) h1 = take(i + 3), m1 = take(i + 4), l1 = take(i + 5);
+                    const int u = two ? t + 1 : t;
+                    L[t] = MF(l0, xs.h, L[t]); if (two) L[u] = MF(l1, xs.h, L[u]);
+                    L[t] = MF(h0, xs.l, L[t]); if (two) L[u] = MF(h1, xs.l, L[u]);
+                    L[t] = MF(m0, xs.m, L[t]); if (two) L[u] = MF(m1, xs.m, L[u]);
+                    L[t] = MF(m0, xs.h, L[t]); if (two) L[u] = MF(m1, xs.h, L[u]);
+                    L[t] = MF(h0, xs.m, L[t]); if (two) L[u] = MF(h1, xs.m, L[u]);
+                    L[t] = MF(h0, xs.h, L[t]); if (two) L[u] = MF(h1, xs.h, L[u]);
+                    if (s + 1 < NS && t < 8) {
+                        vn[t] = cos_feat(dt, 32 * (s + 1) + 8 * g + t);
+                        vn[t + 1] = cos_feat(dt, 32 * (s + 1) + 8 * g + t + 1);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (s + 1 < NS) xs = split8(vn);
+            }
+        }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) sum += L[t][0] + L[t][1] + L[t][2] + L[t][3];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = sum;
+}
+
+template <int MODE>
+static void run_lin_ev(const char *name, const void *w, float *out, int blocks, int iters) {
+    lin_ev<MODE><<<blocks, 256>>>(w, iters, out);
+    hipDeviceSynchronize();
+    hipEvent_t a, b;
+    hipEventCreate(&a);
+    hipEventCreate(&b);
+    hipEventRecord(a);
+    const int reps = 5;
+    for (int r = 0; r < reps; ++r) lin_ev<MODE><<<blocks, 256>>>(w, iters, out);
+    hipEventRecord(b);
+    hipEventSynchronize(b);
+    float ms;
+    hipEventElapsedTime(&ms, a, b);
+    ms /= reps;
+    const double flop = 2.0 * 192 * 176 * 16 * (double)iters * blocks * 4;   // fp32-equivalent
+    printf("lin_event %-16s %.3f ms  %.1f TFLOP/s (fp32-equivalent), %.0f ns per 16-column pass\n", name, ms,
+           flop / ms / 1e9, ms * 1e6 / iters);
+}
+
 int main() {
     void *w;
     const size_t bytes = 4 * 8 * 4 * 3 * 64 * 16;   // 4 layers, bf16x3 packing (largest)
@@ -190,5 +306,7 @@ int main() {
         run<3>("bf16x3 3-prod", w, out, blocks, 200, lds);
         run<7>("bf16x3 6-prod pair", w, out, blocks, 200, lds);
     }
+    run_lin_ev<0>("f32 16x16x4", w, out, blocks, 200);
+    run_lin_ev<6>("bf16x3 6-prod", w, out, blocks, 200);
     return 0;
 }

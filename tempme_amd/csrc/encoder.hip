@@ -618,7 +618,8 @@ __device__ __forceinline__ void rgemm2(const Lin &L, const floatx4 (&x)[NQ], con
 // tm_weights::buf -- the folded region (FoldLay) first, then the reference layers in
 // tm_weights_create's order; compile-time for a kernel instance (NQE = lin_event's K steps), so every
 // weight fragment is one buffer load off a single resource with a constant offset.  The host checks the
-// live pointers against it before the launch (walk_layout_ok).
+// live pointers against it before the launch (walk_layout_ok).  (The kernel reads lin_event's weights from the
+// split pack EncW::ev3, not from EV: EV is gcn_kernel's and the edge table's.)
 template <int NQE>
 struct WalkLay {
     static constexpr int EV = FoldLay::SIZE, EVB = EV + 11 * NQE * 256, G1 = EVB + 176, G1B = G1 + 4 * 11 * 256,
@@ -780,7 +781,8 @@ __device__ __forceinline__ void cgemm2(__amdgpu_buffer_rsrc_t wr, const floatx4 
 // four register moves).
 template <int NQE, int NTD>
 struct WalkConsts {
-    static constexpr int XW = 0, XP = XW + 16 * NQE, EV = XP + 16 * NQE, EVC = EV + 16 * NTD, DEVC = EVC + 16 * NTD,
+    static constexpr int NS = (NQE + 1) / 2;   // lin_event's 32-wide K steps (XW / XP padded to them)
+    static constexpr int XW = 0, XP = XW + 32 * NS, EV = XP + 32 * NS, EVC = EV + 16 * NTD, DEVC = EVC + 16 * NTD,
                          G1 = DEVC + 16 * NTD, G1C = G1 + HID, V0 = G1C + HID, CP = V0 + 2 * HID,
                          U = CP + HID, M2 = U + 2 * HID, M3 = M2 + HID, TC = M3 + HID, M3B = TC + 13 * 80,
                          C0 = M3B + 1, SIZE = M3B + 4;
@@ -899,14 +901,17 @@ __device__ __forceinline__ PosIn load_pos(const WalkArgs &a, int64_t gw, int p, 
     return r;
 }
 
-// edge-feature part of x: unconditional (clamped) loads, all in flight together
+// edge-feature part of x: unconditional (clamped) loads, all in flight together.  lin_event's K steps are 32
+// wide (v_mfma_f32_16x16x32_bf16: lane group g holds k = 32s + 8g + 0..7): ef[2s + hh][r] is this lane's
+// feature k = 32s + 8g + 4hh + r
 __device__ __forceinline__ void load_ef(const WalkArgs &a, int32_t e, float (&ef)[4][4]) {
     const int g = lane_id() >> 4, de = a.P.de;
     const float *erow = a.e_feat + (int64_t)e * de;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        if ((de & 3) == 0 && 16 * q + 16 <= de) {         // whole K step inside the row: one float4
-            const float4 v = *reinterpret_cast<const float4 *>(erow + 16 * q + 4 * g);
+        const int k0 = 32 * (q >> 1) + 8 * g + 4 * (q & 1);
+        if ((de & 3) == 0 && 32 * (q >> 1) + 32 <= de) {  // whole K step inside the row: one float4
+            const float4 v = *reinterpret_cast<const float4 *>(erow + k0);
             ef[q][0] = v.x;
             ef[q][1] = v.y;
             ef[q][2] = v.z;
@@ -914,62 +919,68 @@ __device__ __forceinline__ void load_ef(const WalkArgs &a, int32_t e, float (&ef
         } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const int k = 16 * q + 4 * g + s;
-                ef[q][s] = (16 * q < de) ? erow[k < de ? k : de - 1] : 0.f;
+                const int k = k0 + s;
+                ef[q][s] = (32 * (q >> 1) < de) ? erow[k < de ? k : de - 1] : 0.f;
             }
         }
     }
 }
 
-// Element s of K step q of the event features x[k] = [E(e) | cnt | cos(dt * w + phi)] (:176-179,
-// TimeEncode :45-59) for this lane's feature k = 16q + 4g + s, with the step's time-encoder frequency w
-// and phase ph in registers.  PURE (a step holding only time features, known at compile time): the cos
-// alone.  Otherwise the cos is evaluated unconditionally (the opaque asm keeps the compiler from wrapping
-// the polynomial in an exec-mask branch, which serialised it against the MFMAs) and the count / edge
-// lanes select their values.  Padding lanes (k >= kev) keep cos(0) = 1: lin_event's packed weights are
-// zero there.  In table mode the edge lanes are 0 (their product comes from the table row).
+// lin_event on v_mfma_f32_16x16x32_bf16 (K steps of 32; the D tile has v_mfma_f32_16x16x4_f32's lane layout, so
+// event_gcn and everything after it are unchanged): both fp32 operands are split exactly into three bf16 parts,
+// x = hi + mid + lo (the weights at pack time, EncW::ev3 / split3; the generated features in registers,
+// split_put), and a (tile, step) is the six products down to 2^-16 relative in one fixed order, small terms
+// first: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi, all into the tile's fp32 accumulator.  The dropped
+// products (mid*lo, lo*mid, lo*lo) are below 2^-24 relative, one fp32 rounding.  The same code runs in every
+// instance, so a column's lin_event does not depend on the instance.  (A non-finite feature gives NaN here.)
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+struct Split3 {
+    bf16x8 h, m, l;
+};
+// element j of a step's split features (micro/split.hip's split8: round to nearest, exact residuals)
+__device__ __forceinline__ void split_put(Split3 &x, int j, float v) {
+    const __bf16 h = (__bf16)v;
+    const float r = v - (float)h;
+    const __bf16 m = (__bf16)r;
+    x.h[j] = h;
+    x.m[j] = m;
+    x.l[j] = (__bf16)(r - (float)m);
+}
+#define TM_MF32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+
+// this lane's 8 entries of 32-wide K step s of an LDS vector laid out on the event-feature axis
+__device__ __forceinline__ void lds8(const float *v, int s, float (&o)[8]) {
+    const float4 *p = reinterpret_cast<const float4 *>(v + 32 * s + 8 * ((threadIdx.x & 63) >> 4));
+    const float4 a = p[0], b = p[1];
+    o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w, o[4] = b.x, o[5] = b.y, o[6] = b.z, o[7] = b.w;
+}
+
+// Element j of K step s of the event features x[k] = [E(e) | cnt | cos(dt * w + phi)] (:176-179,
+// TimeEncode :45-59) for this lane's feature k = 32s + 8g + j, with the element's time-encoder frequency w
+// and phase ph (zero outside the time block) and edge feature e in registers.  PURE (a step holding only time
+// features, known at compile time): the cos alone.  Otherwise the cos is evaluated unconditionally (the
+// opaque asm keeps the compiler from wrapping the polynomial in an exec-mask branch, which serialised it
+// against the MFMAs) and the count / edge lanes select their values.  Padding lanes (k >= kev) keep
+// cos(0) = 1: lin_event's packed weights are zero there.  In table mode the edge lanes are 0 (their product
+// comes from the table row).
 template <bool ETAB, bool PURE>
-__device__ __forceinline__ float gen_one(int q, int s, float w, float ph, const float (&ef)[EQ_MAX][4], int g,
-                                         int de, float dt, float c0, float c1, float c2) {
+__device__ __forceinline__ float gen_one(int s, int j, float w, float ph, float e, int g, int de, float dt, float c0,
+                                         float c1, float c2) {
+    if (!ETAB && !PURE && 32 * s + 32 <= de) return e;   // a step of edge features alone (wave-uniform)
     float c = time_cos(dt, w, ph);
     if constexpr (PURE) return c;
-    const int k = 16 * q + 4 * g + s;
-    const int qe = q < EQ_MAX ? q : 0;
-    if (!ETAB && 16 * q + 16 <= de) return ef[qe][s];
+    const int k = 32 * s + 8 * g + j;
     asm volatile("" : "+v"(c));
     float v = c;
     if (k < de + 3) v = (k == de) ? c0 : (k == de + 1) ? c1 : c2;
-    if (k < de) v = ETAB ? 0.f : ef[qe][s];
+    if (k < de) v = ETAB ? 0.f : e;
     return v;
 }
 
-// streamed-edge-feature variant (EQ_MAX*16 < de): e4 = this lane's 4 edge features of K step q
-template <int NQE, int NTD>
-__device__ __forceinline__ floatx4 gen_x_s(int q, const float *cs, const float4 &e4, int g, int de, int kev, float dt,
-                                           float c0, float c1, float c2) {
-    using C = WalkConsts<NQE, NTD>;
-    floatx4 xq;
-    const float4 w4 = lds4(cs + C::XW, q), p4 = lds4(cs + C::XP, q);
-    const float wv[4] = {w4.x, w4.y, w4.z, w4.w}, pv[4] = {p4.x, p4.y, p4.z, p4.w}, ev[4] = {e4.x, e4.y, e4.z, e4.w};
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int k = 16 * q + 4 * g + s;
-        float v;
-        if (16 * q + 16 <= de) v = ev[s];
-        else {
-            v = (k < kev) ? time_cos(dt, wv[s], pv[s]) : 0.f;
-            if (k < de + 3) v = (k == de) ? c0 : (k == de + 1) ? c1 : c2;
-            if (k < de) v = ev[s];
-        }
-        xq[s] = v;
-    }
-    return xq;
-}
-
-// this lane's float4 of K step q of an edge-feature row (de % 4 == 0): clamped unconditional load,
-// zero outside the row
-__device__ __forceinline__ float4 ef_step(const float4 *erow4, int q, int g, int de) {
-    const int i = 4 * q + g, n4 = de >> 2;
+// streamed edge features (de % 4 == 0): half hh of this lane's 8 features of K step s of an edge-feature row,
+// clamped unconditional load, zero outside the row
+__device__ __forceinline__ float4 ef_step(const float4 *erow4, int s, int hh, int g, int de) {
+    const int i = 8 * s + 2 * g + hh, n4 = de >> 2;
     const float4 v = erow4[i < n4 ? i : n4 - 1];
     return i < n4 ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
@@ -990,14 +1001,15 @@ __device__ __forceinline__ void load_et(const WalkArgs &a, int32_t e, float4 (&e
 // One walk position for the 16 columns of this wave -> H = [relu(g1 A + b) | relu(g1 B + b)] (8 tiles,
 // B layout), event_gcn's hidden layer of both branches; the second MLP layer (g2) is folded into the
 // layers that read F = [U_s | U_t] (FoldLay).
-// lin_event runs K-outer ((q, t) fragment order): the next K step's 4 event features are generated one
-// element per tile between this step's MFMAs.  Its accumulators start from the bias (LDS) or, in table
-// mode, from the edge's table row (edge-feature product + bias; the slot pass adds the folded time steps).
+// lin_event runs K-outer in 32-wide steps on bf16 MFMA ((step, tile, part) fragment order, see Split3): the next
+// K step's 8 event features are generated and split one element per tile between this step's MFMAs.  Its
+// accumulators start from the bias (LDS) or, in table mode, from the edge's table row (edge-feature product +
+// bias; the slot pass adds the folded time steps).
 // Both nodes' feature rows are requested before the K loop (their latency overlaps it) and consumed
 // in its epilogue.  Tiles past dn in the last node tile hold a clamped duplicate; g1's packed weights are
 // zero for those inputs, so they contribute nothing.
-// SEF (streamed edge features, EQ_MAX*16 < de <= 176): ef holds K steps 0 and 1 (loaded during the
-// previous pass); step q + 2's float4 is loaded while step q's MFMAs run.
+// SEF (streamed edge features, EQ_MAX*16 < de <= 176): ef holds the 32-wide K steps 0 and 1 (loaded during the
+// previous pass); step s + 2's two float4 are loaded while step s's MFMAs run.
 template <int NQE, int NTD, bool SEF, int Q0, bool ZN, class Extra>
 __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs,
                                                 const PosIn &pi, const float (&ef)[EQ_MAX][4],
@@ -1009,7 +1021,7 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
     using LY = WalkLay<NQE>;
     const EncW &P = a.P;
     const int g = lane_id() >> 4;
-    const int de = P.de, dn = P.dn, kev = P.kev;
+    const int de = P.de, dn = P.dn;
     const float dt = pi.v ? pi.tb - pi.ta : 0.f, c0 = pi.v ? pi.c0 : 0.f, c1 = pi.v ? pi.c1 : 0.f,
                 c2 = pi.v ? pi.c2 : 0.f;
     const float4 *nrow_s = reinterpret_cast<const float4 *>(a.n_feat + (int64_t)(pi.v ? pi.ns : 0) * dn);
@@ -1036,119 +1048,131 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         rt[q % JN] = nrow_t[f4];
     };
     {
+        constexpr int NS = C::NS, S0 = Q0 / 2;           // 32-wide K steps; table mode starts at step de / 32
+        constexpr int N = NTD * (NS - S0) * 3, D = 12;   // fragments (tile, step, part); ring depth: 4 (tile, step)s
+        static_assert(D >= PFP && D <= N && D % 3 == 0, "lin_event ring depth");
         const int vo = lane_id() * 16;
-        constexpr int nq = NQE;
-        constexpr int N = NTD * (NQE - Q0), D = PFP;
-        static_assert(D >= PFP && D <= N, "lin_event ring depth");
-        constexpr int EVF4 = LY::EV / 4;
-        // the first D fragments (EVF4 + ((i % NTD) * nq + Q0 + i / NTD) * 64) come in pre, requested during
-        // the previous pass; the ring's last D refills request event_gcn's first K step (G1 tiles 0..3)
+        // the split pack's byte offset off wr in the lane offset, so every fragment offset stays a constant
+        const int vo3 = vo + 16 * (int)(P.ev3 - P.kv.w);
+        // ring order K-outer: fragment i = (step S0 + i / (3 NTD), tile (i / 3) % NTD, part i % 3).  The first PFP
+        // come in pre, requested during the previous pass; the ring's last refills request event_gcn's first K
+        // step (G1 tiles 0..3)
+        auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
+        auto g1f = [](int k) { return LY::G1 / 4 + k * NTD * 64; };
+        // the constant rides on an opaque scalar zero defined inside the pass loop: the ~200 distinct offsets are
+        // then one s_add each where they are used, not hoisted out of the loop into spilled SGPRs (a v_readlane
+        // per load on the VALU pipe, which the feature generation needs)
+        int z3 = 0;
+        asm volatile("" : "+s"(z3));
+        auto wload3 = [&](int i) {
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i) * 16, 0));
+        };
         float4 buf[D];
 #pragma unroll
-        for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload(wr, vo, EVF4 + ((i % NTD) * nq + Q0 + i / NTD) * 64);
-        auto g1f = [](int k) { return LY::G1 / 4 + k * NTD * 64; };
-        const int qend = p == 2 ? P.qt : NQE;            // slot pass: steps >= qt folded into evc / devc
-        if constexpr (SEF) {
-            const float4 *erow4 = reinterpret_cast<const float4 *>(a.e_feat + (int64_t)pi.edge() * de);
-            float4 ring[2];
-            ring[0] = make_float4(ef[0][0], ef[0][1], ef[0][2], ef[0][3]);
-            ring[1] = make_float4(ef[1][0], ef[1][1], ef[1][2], ef[1][3]);
-            floatx4 xq = gen_x_s<NQE, NTD>(0, cs, ring[0], g, de, kev, dt, c0, c1, c2);
+        for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload3(i);
+        const int qend = p == 2 ? P.qt : NS;             // slot pass: steps >= qt folded into evc / devc
+        // this lane's edge features of step s: plain mode from ef (steps 0, 1), streamed (SEF) through a ring
+        // of two steps, step s + 2's requested while step s's MFMAs run; none in table mode
+        const float4 *erow4 = reinterpret_cast<const float4 *>(a.e_feat + (int64_t)pi.edge() * de);
+        float4 ring[2][2];
 #pragma unroll
-            for (int q = 0; q < NQE; ++q) {
-                if (q < qend) {                           // wave-uniform (a break would stop the unrolling)
-                    floatx4 xn = xq;
-                    float4 e2 = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (q + 2 < NQE && 16 * (q + 2) < de) e2 = ef_step(erow4, q + 2, g, de);
-                    if (q + 1 < NQE) xn = gen_x_s<NQE, NTD>(q + 1, cs, ring[(q + 1) & 1], g, de, kev, dt, c0, c1, c2);
+        for (int q = 0; q < 4; ++q) ring[q >> 1][q & 1] = make_float4(ef[q][0], ef[q][1], ef[q][2], ef[q][3]);
+        auto edge = [&](int s, int j) -> float {
+            if (ETAB || (!SEF && s >= 2)) return 0.f;
+            const float4 v = ring[s & 1][j >> 2];
+            return (j & 3) == 0 ? v.x : (j & 3) == 1 ? v.y : (j & 3) == 2 ? v.z : v.w;
+        };
+        // steps holding only time features (compile time): table mode past its first step; plain mode past
+        // de + 3 <= 67
+        auto pure = [](int s) { return ETAB ? s > S0 : (!SEF && s >= 3); };
+        const float *cw = cs + C::XW, *cp = cs + C::XP;
+        Split3 xs;
+        {
+            float w8[8], p8[8];
+            lds8(cw, S0, w8);
+            lds8(cp, S0, p8);
 #pragma unroll
-                    for (int t = 0; t < NTD; ++t) {
-                        const int i = q * NTD + t;
-                        const float4 w = buf[i % D];
-                        if (i + D < N) buf[i % D] = wload(wr, vo, EVF4 + (((i + D) % NTD) * nq + (i + D) / NTD) * 64);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, xq.x, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, xq.y, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, xq.z, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, xq.w, L[t], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    ring[q & 1] = e2;
-                    xq = xn;
+            for (int j = 0; j < 8; ++j)
+                split_put(xs, j, gen_one<ETAB, false>(S0, j, w8[j], p8[j], edge(S0, j), g, de, dt, c0, c1, c2));
+        }
+#pragma unroll
+        for (int s = S0; s < NS; ++s) {
+            if (s < qend) {                               // wave-uniform (a break would stop the unrolling)
+                // step s + 1's constants from LDS now (first use after the first tile pair's MFMAs)
+                float w8[8] = {}, p8[8] = {};
+                if (s + 1 < NS) {
+                    lds8(cw, s + 1, w8);
+                    lds8(cp, s + 1, p8);
                 }
-            }
-        } else {
-            const float *cw = cs + C::XW, *cp = cs + C::XP;
-            floatx4 xq;
-            {
-                const float4 w4 = lds4(cw, Q0), p4 = lds4(cp, Q0);
-                xq[0] = gen_one<ETAB, false>(Q0, 0, w4.x, p4.x, ef, g, de, dt, c0, c1, c2);
-                xq[1] = gen_one<ETAB, false>(Q0, 1, w4.y, p4.y, ef, g, de, dt, c0, c1, c2);
-                xq[2] = gen_one<ETAB, false>(Q0, 2, w4.z, p4.z, ef, g, de, dt, c0, c1, c2);
-                xq[3] = gen_one<ETAB, false>(Q0, 3, w4.w, p4.w, ef, g, de, dt, c0, c1, c2);
-            }
-#pragma unroll
-            for (int q = Q0; q < NQE; ++q) {
-                if (q < qend) {                           // wave-uniform (a break would stop the unrolling)
-                    // step q + 1's constants from LDS now (first use after tile 0's MFMAs)
-                    float4 w4 = make_float4(0.f, 0.f, 0.f, 0.f), p4 = w4;
-                    if (q + 1 < NQE) {
-                        w4 = lds4(cw, q + 1);
-                        p4 = lds4(cp, q + 1);
+                float4 e2[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+                if constexpr (SEF) {
+                    if (s + 2 < NS && 32 * (s + 2) < de) {
+                        e2[0] = ef_step(erow4, s + 2, 0, g, de);
+                        e2[1] = ef_step(erow4, s + 2, 1, g, de);
                     }
-                    const float wq[4] = {w4.x, w4.y, w4.z, w4.w}, pq[4] = {p4.x, p4.y, p4.z, p4.w};
-                    constexpr bool pure_next_ok = ETAB;   // table mode: steps >= Q0 + 2 hold only time features
-                    floatx4 xn = xq;
-                    auto gen = [&](int t) {
-                        if (q + 1 < NQE && t < 4) {
-                            if (pure_next_ok && q + 1 >= Q0 + 2)
-                                xn[t] = gen_one<ETAB, true>(q + 1, t, wq[t], pq[t], ef, g, de, dt, c0, c1, c2);
-                            else
-                                xn[t] = gen_one<ETAB, false>(q + 1, t, wq[t], pq[t], ef, g, de, dt, c0, c1, c2);
-                        }
-                    };
-                    auto wnext = [&](int i) {   // fragment i + D of the ring into slot i % D (past N: G1's)
-                        if (i + D < N) buf[i % D] = wload(wr, vo, EVF4 + (((i + D) % NTD) * nq + Q0 + (i + D) / NTD) * 64);
-                        else if (i + D - N < PFP) buf[i % D] = wload(wr, vo, g1f(i + D - N));
-                    };
-                    // tile pairs with interleaved MFMAs (no MFMA waits on its predecessor); an odd last tile alone
-#pragma unroll
-                    for (int t = 0; t + 1 < NTD; t += 2) {
-                        const int i = (q - Q0) * NTD + t;
-                        const float4 w0 = buf[i % D];
-                        wnext(i);
-                        const float4 w1 = buf[(i + 1) % D];
-                        wnext(i + 1);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, xq.x, L[t], 0, 0, 0);
-                        L[t + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, xq.x, L[t + 1], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, xq.y, L[t], 0, 0, 0);
-                        L[t + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, xq.y, L[t + 1], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, xq.z, L[t], 0, 0, 0);
-                        L[t + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, xq.z, L[t + 1], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, xq.w, L[t], 0, 0, 0);
-                        L[t + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, xq.w, L[t + 1], 0, 0, 0);
-                        gen(t);
-                        gen(t + 1);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if constexpr (NTD % 2) {
-                        constexpr int t = NTD - 1;
-                        const int i = (q - Q0) * NTD + t;
-                        const float4 w = buf[i % D];
-                        wnext(i);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.x, xq.x, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.y, xq.y, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.z, xq.z, L[t], 0, 0, 0);
-                        L[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w.w, xq.w, L[t], 0, 0, 0);
-                        gen(t);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    xq = xn;
                 }
+                Split3 xn = xs;
+                // element j of step s + 1, generated and split between this step's MFMAs (one per tile, tiles 0..7)
+                auto gen = [&](int j) {
+                    if (s + 1 < NS && j < 8) {
+                        const float e = edge(s + 1, j);
+                        const float v = pure(s + 1) ? gen_one<ETAB, true>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2)
+                                                    : gen_one<ETAB, false>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2);
+                        split_put(xn, j, v);
+                    }
+                };
+                // fragment i out of the ring; its slot takes fragment i + D (past N: G1's first)
+                auto take = [&](int i) {
+                    const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
+                    if (i + D < N) buf[i % D] = wload3(i + D);
+                    else if (i + D - N < PFP) buf[i % D] = wload(wr, vo, g1f(i + D - N));
+                    return v;
+                };
+                // tile pairs with interleaved MFMAs (no MFMA waits on its predecessor); an odd last tile alone
+#pragma unroll
+                for (int t = 0; t + 1 < NTD; t += 2) {
+                    const int i = ((s - S0) * NTD + t) * 3;
+                    const bf16x8 h0 = take(i), m0 = take(i + 1), l0 = take(i + 2);
+                    const bf16x8 h1 = take(i + 3), m1 = take(i + 4), l1 = take(i + 5);
+                    L[t] = TM_MF32(l0, xs.h, L[t]);
+                    L[t + 1] = TM_MF32(l1, xs.h, L[t + 1]);
+                    L[t] = TM_MF32(h0, xs.l, L[t]);
+                    L[t + 1] = TM_MF32(h1, xs.l, L[t + 1]);
+                    L[t] = TM_MF32(m0, xs.m, L[t]);
+                    L[t + 1] = TM_MF32(m1, xs.m, L[t + 1]);
+                    L[t] = TM_MF32(m0, xs.h, L[t]);
+                    L[t + 1] = TM_MF32(m1, xs.h, L[t + 1]);
+                    L[t] = TM_MF32(h0, xs.m, L[t]);
+                    L[t + 1] = TM_MF32(h1, xs.m, L[t + 1]);
+                    L[t] = TM_MF32(h0, xs.h, L[t]);
+                    L[t + 1] = TM_MF32(h1, xs.h, L[t + 1]);
+                    gen(t);
+                    gen(t + 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (NTD % 2) {
+                    constexpr int t = NTD - 1;
+                    const int i = ((s - S0) * NTD + t) * 3;
+                    const bf16x8 h0 = take(i), m0 = take(i + 1), l0 = take(i + 2);
+                    L[t] = TM_MF32(l0, xs.h, L[t]);
+                    L[t] = TM_MF32(h0, xs.l, L[t]);
+                    L[t] = TM_MF32(m0, xs.m, L[t]);
+                    L[t] = TM_MF32(m0, xs.h, L[t]);
+                    L[t] = TM_MF32(h0, xs.m, L[t]);
+                    L[t] = TM_MF32(h0, xs.h, L[t]);
+                    gen(t);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (SEF) {
+                    ring[s & 1][0] = e2[0];
+                    ring[s & 1][1] = e2[1];
+                }
+                xs = xn;
             }
         }
-        // G1's first fragments: in the ring's slots after a full K loop; the slot pass (K loop cut at qt) and
-        // the streamed-edge-feature loop request them now
-        if (SEF || p == 2) {
+        // G1's first fragments: in the ring's slots after a full K loop; the slot pass (K loop cut at qt)
+        // requests them now
+        if (p == 2) {
 #pragma unroll
             for (int k = 0; k < PFP; ++k) buf[(N + k) % D] = wload(wr, vo, g1f(k));
         }
@@ -1492,10 +1516,11 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     PosIn cur = load_pos(a, eg * a.W + (int64_t)j * a.M, 2, valid);
     float ef[EQ_MAX][4] = {};
     float4 et[ETAB_N(QE0)];
-    // lin_event's first PFP fragments (ring order: tile k % NTD, K step QE0 + k / NTD), carried pass to pass
+    // lin_event's first PFP fragments (ring order: tile 0's hi / mid / lo and tile 1's hi of its first 32-wide K
+    // step QE0 / 2, in the split pack EncW::ev3), carried pass to pass
     NextFr lin0;
 #pragma unroll
-    for (int k = 0; k < PFP; ++k) lin0.o[k] = WalkLay<NQE>::EV / 4 + ((k % NTD) * NQE + QE0 + k / NTD) * 64;
+    for (int k = 0; k < PFP; ++k) lin0.o[k] = (int)(P.ev3 - P.kv.w) + (((k / 3) * C::NS + QE0 / 2) * 3 + k % 3) * 64;
     float4 pre[PFP];
 #pragma unroll
     for (int k = 0; k < PFP; ++k) pre[k] = wload(wr, lane_id() * 16, lin0.o[k]);
@@ -1706,7 +1731,8 @@ static bool walk_layout_ok(const EncW &P, int nqe) {
                                                                      4 * 4 * 256 + 64 + 5 * 5 * 256 + 80;
     return at(P.ev.w, ev) && at(P.g1.w, g1) && at(P.m2.w, m2) && at(P.a1d.w, FoldLay::A1D) &&
            at(P.a1g.w, FoldLay::A1G) && at(P.m1a2.w, FoldLay::M1A2) && at(P.kvz.w, FoldLay::KVZ) &&
-           at(P.a1dz.w, FoldLay::A1DZ) && at(P.a1gz.w, FoldLay::A1GZ) && P.g1.nt == 4 && P.g1.nq == 11 && P.m2.nt == 4 && P.m2.nq == 5 && P.ev.nt == 11 && P.ev.nq == nqe;
+           at(P.a1dz.w, FoldLay::A1DZ) && at(P.a1gz.w, FoldLay::A1GZ) && P.g1.nt == 4 && P.g1.nq == 11 && P.m2.nt == 4 && P.m2.nq == 5 && P.ev.nt == 11 && P.ev.nq == nqe &&
+           P.ev3 && P.ns3 == (nqe + 1) / 2;
 }
 
 // ------------------------------------------------------------------ per-edge dependency gate table
@@ -2043,6 +2069,10 @@ extern "C" int tm_weights_create_ex(int32_t de, int32_t dn, int32_t h, int32_t i
     const size_t ph = total; total += r16(dn);
     const size_t evc = total; total += r16(dn);
     const size_t devc = total; total += r16(dn);
+    // lin_event's three-way bf16 split pack (EncW::ev3): 3 fragments of 256 floats per (tile, 32-wide K step)
+    const int ns3 = (P.kev + 31) / 32;
+    total = (total + 63) & ~(size_t)63;
+    const size_t ev3 = total; total += (size_t)(r16(dn) / 16) * ns3 * 3 * 256;
     int prev = 0;
     (void)hipGetDevice(&prev);
     if (hipSetDevice(device) != hipSuccess || hipMalloc(&w->buf, total * sizeof(float)) != hipSuccess ||
@@ -2066,7 +2096,9 @@ extern "C" int tm_weights_create_ex(int32_t de, int32_t dn, int32_t h, int32_t i
     P.phase = w->buf + ph;
     P.evc = w->buf + evc;
     P.devc = w->buf + devc;
-    P.qt = (de + 3 + 15) / 16;
+    P.qt = (de + 3 + 31) / 32;
+    P.ev3 = reinterpret_cast<const float4 *>(w->buf + ev3);
+    P.ns3 = ns3;
     {   // folded packs (tmk::FoldLay)
         using F = tmk::FoldLay;
         struct FL {
@@ -2113,6 +2145,10 @@ static std::atomic<uint64_t> g_weights_stamp{0};
 void tm_weights_bump(tm_weights *w) { w->version = g_weights_stamp.fetch_add(1, std::memory_order_relaxed) + 1; }
 
 extern "C" uint64_t tm_weights_version(const tm_weights *w) { return w ? w->version : 0; }
+
+extern "C" void tm_weight_split3(const float *in, int64_t n, uint16_t *hi, uint16_t *mid, uint16_t *lo) {
+    for (int64_t i = 0; i < n; ++i) split3(in[i], hi[i], mid[i], lo[i]);
+}
 
 extern "C" int tm_weights_set_node_zero(tm_weights *w, int32_t node_zero) {
     if (!w) return fail(TM_E_ARG, "tm_weights_set_node_zero: NULL weights");

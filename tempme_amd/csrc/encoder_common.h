@@ -26,7 +26,13 @@ struct EncW {
     // lin_event bias plus the K steps q >= qt (all time features) at dt = 0: walk position 2 is
     // relative to itself, so those steps are the constant cos(phase) (walk_kernel's slot pass)
     const float *evc;
-    int qt;
+    int qt;   // in the walk kernel's 32-wide K steps: (de + 3 + 31) / 32
+    // lin_event's weights for the walk kernel's bf16 MFMA form (split3): per (output tile t, K step s of 32,
+    // part hi / mid / lo) one 1 KB fragment in v_mfma_f32_16x16x32_bf16's A-operand lane order -- lane l holds
+    // row 16t + (l & 15), k = 32s + 8(l >> 4) + 0..7 -- at float4 offset ((t * ns3 + s) * 3 + part) * 64;
+    // rows >= dn and k >= kev are zero.  In tm_weights::buf, so one buffer resource reaches it.
+    const float4 *ev3;
+    int ns3;
     // lin_event's folded time steps alone (evc - bias, fp64 sum rounded once): the table-mode slot pass,
     // whose edge-table row already carries the bias
     const float *devc;
@@ -114,6 +120,33 @@ __device__ __forceinline__ int ecol(int nt) { return nt * 16 + (threadIdx.x & 15
 __device__ __forceinline__ float time_cos(float t, float w, float phi) { return cos_rd(__fadd_rn(__fmul_rn(t, w), phi)); }
 
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
+
+// ------------------------------------------------------------------ exact three-way bf16 split of an fp32 value
+// bf16 bit pattern of v rounded to nearest even; a finite v whose round-up would reach the infinity pattern
+// truncates instead (stays the largest finite bf16), NaN keeps a mantissa bit
+__host__ __device__ inline uint16_t bf16_rne_bits(float v) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
+    const uint32_t r = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+    return (uint16_t)((r & 0x7f80u) == 0x7f80u ? (u >> 16) : r);
+}
+__host__ __device__ inline float bf16_bits_f32(uint16_t b) { return __builtin_bit_cast(float, (uint32_t)b << 16); }
+// v = hi + mid + lo (micro/split.hip's split8, one element): both residuals are exact fp32 differences, and the
+// last one fits bf16's 8 bits whenever it stays above bf16's denormal step (|v| >= 2^-110); non-finite v: hi alone
+__host__ __device__ inline void split3(float v, uint16_t &hi, uint16_t &mid, uint16_t &lo) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, v);
+    hi = bf16_rne_bits(v);
+    mid = lo = 0;
+    if ((u & 0x7f800000u) == 0x7f800000u) return;
+    const float r1 = v - bf16_bits_f32(hi);
+    // hi truncated (the top binade's last bf16 step): mid truncates too, or hi + mid would round up to inf
+    const bool trunc = (hi & 0x7fffu) == 0x7f7fu && (u & 0xffffu) >= 0x8000u;
+    mid = trunc ? (uint16_t)(__builtin_bit_cast(uint32_t, r1) >> 16) : bf16_rne_bits(r1);
+    lo = bf16_rne_bits(r1 - bf16_bits_f32(mid));
+    // a zero part takes the value's sign, so that -0 = (-0) + (-0) + (-0) bit for bit
+    if ((mid & 0x7fffu) == 0) mid = hi & 0x8000u;
+    if ((lo & 0x7fffu) == 0) lo = hi & 0x8000u;
+}
 
 // The dependency gate's logit d3 . G2 over its h2 = h/2 features in ONE fixed order, shared by the
 // LDS-tiled kernels and the register-resident gate_reg_kernel (h2 = 32) so their gates agree bit for bit:

@@ -34,6 +34,7 @@ struct PackJob {
     const float *src;
     float *dst;
     int32_t so, sc, nout, k, nt, nq;
+    int32_t split;   // 1: the three-way bf16 split pack of EncW::ev3 (nq = its 32-wide K steps; dst in bf16 units)
     int64_t begin;
 };
 constexpr int MAX_PACK_JOBS = 56;
@@ -53,6 +54,18 @@ __global__ void pack_jobs_kernel(PackJobs J) {
             p.dst[e] = e < p.nout ? p.src[e] : 0.f;
             continue;
         }
+        if (p.split) {   // element (t, s, lane, j) -> its hi / mid / lo fragments (512 bf16 each)
+            const int j = e & 7, l = (e >> 3) & 63;
+            const int64_t ts = e >> 9;
+            const int o = 16 * (int)(ts / p.nq) + (l & 15), c = 32 * (int)(ts % p.nq) + 8 * (l >> 4) + j;
+            uint16_t hi, mid, lo;
+            split3((o < p.nout && c < p.k) ? p.src[(int64_t)o * p.so + (int64_t)c * p.sc] : 0.f, hi, mid, lo);
+            uint16_t *d = reinterpret_cast<uint16_t *>(p.dst) + ts * 3 * 512 + l * 8 + j;
+            d[0] = hi;
+            d[512] = mid;
+            d[1024] = lo;
+            continue;
+        }
         const int s = e & 3, l = (e >> 2) & 63;
         const int64_t tq = e >> 8;
         const int q = (int)(tq % p.nq), t = (int)(tq / p.nq);
@@ -61,7 +74,7 @@ __global__ void pack_jobs_kernel(PackJobs J) {
     }
 }
 
-// evc[f] = b[f] + sum_{k >= 16 qt} W[f][k] * cos(0 * w + phi): one wave per output feature, fp64
+// evc[f] = b[f] + sum_{k >= 32 qt} W[f][k] * cos(0 * w + phi): one wave per output feature, fp64
 // partial sums combined in a fixed butterfly order, one rounding to fp32 (walk_kernel's slot pass);
 // devc[f] = the same sum without the bias (the table-mode slot pass: the edge-table row carries the bias)
 __global__ void __launch_bounds__(64) evc_par_kernel(const float *__restrict__ W, const float *__restrict__ b,
@@ -70,7 +83,7 @@ __global__ void __launch_bounds__(64) evc_par_kernel(const float *__restrict__ W
     const int f = blockIdx.x, lane = threadIdx.x;
     double acc = 0.0;
     if (f < dn)
-        for (int k = 16 * qt + lane; k < kev; k += 64) acc += (double)W[(int64_t)f * kev + k] * (double)cos_rd(phase[k - de - 3]);
+        for (int k = 32 * qt + lane; k < kev; k += 64) acc += (double)W[(int64_t)f * kev + k] * (double)cos_rd(phase[k - de - 3]);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (lane == 0) {
         out[f] = f < dn ? (float)(acc + (double)b[f]) : 0.f;
@@ -1598,6 +1611,20 @@ void pack_all_weights(tm_weights *w, const float *const *t, hipStream_t s) {
         p.begin = total;
         total += npad;
     };
+    {   // lin_event's split pack for the walk kernel (EncW::ev3), from the same raw tensor as its fp32 pack
+        PackJob &p = P.j[P.n++];
+        p.src = t[0];
+        p.dst = const_cast<float *>(reinterpret_cast<const float *>(w->P.ev3));
+        p.so = kev;
+        p.sc = 1;
+        p.nout = dn;
+        p.k = kev;
+        p.nt = w->P.ev.nt;
+        p.nq = w->P.ns3;
+        p.split = 1;
+        p.begin = total;
+        total += (int64_t)p.nt * p.nq * 512;
+    }
     for (auto &sp : w->specs) {           // forward packs of W[nout][k] and their biases
         frag(*sp.lin, t[sp.wi], sp.k, 1);
         copy(t[sp.wi + 1], sp.lin->b, sp.nout, sp.lin->nt * 16);

@@ -339,6 +339,47 @@ typedef struct {
 int tm_wgrad(const tm_wgrad_job *jobs, int32_t n_jobs, const tm_wgrad_target *targets, int32_t n_targets,
              void *stream);
 
+/* ---------------------------------------------------------------- pooled encoder training (device)
+ * enhance_predict_walks (explainer_new.py:221-258) under autograd, as enhance_main.py's training loop runs it:
+ * the differentiable twin of tm_encoder_pool_fwd, for the dims tm_encoder_train_supported accepts.
+ *
+ * Workspace bytes tm_encoder_pool_train_fwd needs for n_walks walks: the event_gcn outputs F and the groups' std
+ * (kept for tm_encoder_pool_bwd), then the per-walk partial rows [n_walks][h]. */
+int64_t tm_encoder_pool_train_workspace_bytes(const tm_weights *w, int64_t n_walks);
+
+/* Forward: the inputs of tm_encoder_train_fwd plus the walk weights wgt [G,B,W] (tm_walk_importance; constants of
+ * the graph, they get no gradient) -> out as tm_encoder_pool_fwd writes it (h pooled columns, then the 12-bin
+ * histogram with the category feature; rows ld_out >= h (+ 12) floats apart).  drop (nullable = no dropout) has
+ * tm_encoder_train_fwd's layout [n_walks][DC]: columns 0..1 mask alpha (:839), the next h attention.MLP's hidden
+ * layer (:780); the MLP-hidden columns are ignored (the scoring MLP is not part of this function), and with
+ * use_temporal_guidance=False all of them are.  The tail's identity holds with h_w the dropped-out hidden layer:
+ * sum_w wgt_w (A2 h_w + b2) = A2 sum_w wgt_w h_w + b2 sum_w wgt_w.  Runs the LDS-tiled kernels of
+ * tm_encoder_train_fwd (never the fused walk kernel); fixed summation orders, bitwise reproducible. */
+int tm_encoder_pool_train_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
+                              int32_t B, int32_t W, const int32_t *node6, const int32_t *eid3, const float *ts3,
+                              const int32_t *cat, const double *cut, const float *cnt, const float *wgt,
+                              const uint8_t *drop, float drop_scale, void *workspace, float *out, int64_t ld_out,
+                              void *stream);
+
+/* Backward of tm_encoder_pool_train_fwd given d_emb = dL/d out (rows ld_demb >= h floats apart, e.g. the
+ * [G,B,node_emd_dim] gradient: only each row's leading h columns are read), with the same inputs, masks and
+ * workspace.  d attention.MLP's output of walk w is wgt[w] * d_emb[event of w]; from there on the chain rule
+ * of tm_encoder_bwd.  io: the buffers of tm_encoder_bwd, of which dY2 .. dt are written; the scoring MLP's six
+ * (dlogit, M2, dM2, M1d, dM1, X) and imp are not touched and may be NULL. */
+int tm_encoder_pool_bwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups, int32_t B,
+                        int32_t W, const int32_t *node6, const int32_t *eid3, const float *ts3, const int32_t *cat,
+                        const double *cut, const float *cnt, const float *wgt, const uint8_t *drop, float drop_scale,
+                        const void *workspace, const float *d_emb, int64_t ld_demb, const tm_encoder_grad_io *io,
+                        void *stream);
+
+/* Weight gradients of the pooled encoder from tm_encoder_pool_bwd's buffers: grads = 16 DEVICE pointers, written
+ * (not accumulated), tm_encoder_wgrad's list without MLP.0 / .3 / .5 in the same order: lin_event w/b,
+ * event_conv.MLP.0 w/b, .MLP.2 w/b, attention.W1 w/b, .W2 w/b, .MLP.0 w/b, .MLP.3 w/b,
+ * time_encoder.basis_freq, .phase.  The same deterministic reductions. */
+#define TM_N_POOL_GRADS 16
+int tm_encoder_pool_wgrad(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W, const tm_encoder_grad_io *io,
+                          const void *workspace, float *const *grads, void *stream);
+
 /* retrieve_edge_imp_node in training (explainer_new.py:354-406 with dropout in the dependency gate,
  * :367-386) up to the gathered scatter-max values: p1 [G,B,N] and p2 [G,B,N^2] are the per-edge maxima
  * of imp * (0.5 + 0.5 sigmoid(gate)) gathered at the subgraph edge ids BEFORE beta_sample and the

@@ -39,6 +39,7 @@ EXPORTS = (
     "tm_sample_events", "tm_gather_rows", "tm_weights_create", "tm_weights_create_ex", "tm_weights_pack", "tm_weights_variant", "tm_weights_set_node_zero", "tm_weights_version", "tm_weights_free",
     "tm_weight_split3", "tm_encoder_workspace_bytes",
     "tm_walk_importance", "tm_encoder_pool_workspace_bytes", "tm_encoder_pool_fwd",
+    "tm_encoder_pool_train_workspace_bytes", "tm_encoder_pool_train_fwd", "tm_encoder_pool_bwd", "tm_encoder_pool_wgrad",
     "tm_encoder_fwd", "tm_encoder_fwd_tab", "tm_encoder_train_supported", "tm_encoder_train_fwd", "tm_encoder_bwd", "tm_encoder_wgrad", "tm_wgrad",
     "tm_explain_train_fwd", "tm_explain_train_fwd_pad", "tm_explain_train_bwd", "tm_kl_loss", "tm_edge_importance", "tm_edge_gate_table",
     "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_tgat_attn_fwd", "tm_tgat_attn_bwd", "tm_tgat_merge_fwd", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
@@ -192,6 +193,13 @@ def _sig(L):
     L.tm_encoder_pool_workspace_bytes.restype = i64
     L.tm_encoder_pool_workspace_bytes.argtypes = [vp, i64]
     L.tm_encoder_pool_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.tm_encoder_pool_train_workspace_bytes.restype = i64
+    L.tm_encoder_pool_train_workspace_bytes.argtypes = [vp, i64]
+    L.tm_encoder_pool_train_fwd.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp,
+                                            i64, vp]
+    L.tm_encoder_pool_bwd.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, vp, vp, i64,
+                                      C.POINTER(EncoderGradIO), vp]
+    L.tm_encoder_pool_wgrad.argtypes = [vp, i32, i32, i32, C.POINTER(EncoderGradIO), vp, C.POINTER(vp), vp]
     L.tm_edge_importance_tab.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tm_gm_packed_floats.restype = i64
     L.tm_gm_packed_floats.argtypes = [i32, i32]
@@ -230,7 +238,8 @@ def _sig(L):
     L.tm_beta_rsample_bwd.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
     L.tm_profile_entry.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(i64)]
     for name in EXPORTS:
-        if name not in ("tm_last_error", "tm_encoder_workspace_bytes", "tm_encoder_pool_workspace_bytes"):
+        if name not in ("tm_last_error", "tm_encoder_workspace_bytes", "tm_encoder_pool_workspace_bytes",
+                        "tm_encoder_pool_train_workspace_bytes"):
             getattr(L, name).restype = C.c_int
 
 

@@ -243,7 +243,8 @@ __global__ void __launch_bounds__(256) gcn_kernel(EncW P, int64_t n_rows, const 
 // ------------------------------------------------------------------ attention head + final MLP: TR walks per block
 // TR = 32, or 16 where the 32-walk tiles exceed the LDS (hid_dim above 152)
 // POOL (tm_encoder_pool_fwd): the kernel ends at attention.MLP's hidden layer and writes out[walk][h] =
-// wgt[walk] * relu(attention.MLP.0 O) (zero in the padded columns) for pool_tail_kernel to sum per event
+// wgt[walk] * relu(attention.MLP.0 O) (zero in the padded columns) for pool_tail_kernel to sum per event; with
+// drop (tm_encoder_pool_train_fwd) the hidden layer's keep-mask is applied before the weight
 template <int TR, bool POOL = false>
 __global__ void __launch_bounds__(256) head_kernel(EncW P, int64_t n_walks, int64_t walks_per_group, int32_t W,
                                                    const float *__restrict__ F, const float *__restrict__ ts3,
@@ -347,7 +348,11 @@ __global__ void __launch_bounds__(256) head_kernel(EncW P, int64_t n_walks, int6
             const int c = ecol(nt);
             for (int r = 0; r < 4; ++r) {
                 const int64_t gw = w0 + erow(mt, r);
-                if (gw < n_walks) out[gw * h + c] = wgt[gw] * relu(acc[r] + P.a1.b[c]);
+                if (gw >= n_walks) continue;
+                float v = relu(acc[r] + P.a1.b[c]);
+                if (drop && P.tg)   // tm_encoder_pool_train_fwd: TemporalAwareAttention.MLP's Dropout (:780)
+                    v = drop[gw * drop_cols(h, P.hm) + DROP_H + c] ? v * dscale : 0.f;
+                out[gw * h + c] = wgt[gw] * v;
             }
         });
         return;
@@ -2574,6 +2579,61 @@ extern "C" int tm_encoder_train_fwd(const tm_weights *w, const float *n_feat, co
     launch_head(P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, out_imp, drop, drop_scale, s);
     TM_CHECK_LAUNCH();
     prof_end("head_kernel", s, pe);
+    return TM_OK;
+}
+
+// the workspace of tm_encoder_pool_train_fwd: tm_encoder_train_fwd's (F and the groups' std, kept for
+// tm_encoder_pool_bwd), then the per-walk partial rows [n_walks][h]
+extern "C" int64_t tm_encoder_pool_train_workspace_bytes(const tm_weights *w, int64_t n_walks) {
+    return pool_part_offset(w, n_walks) + n_walks * (w ? w->h : HID) * (int64_t)sizeof(float) + 256;
+}
+
+// Training forward of the pooled encoder (enhance_predict_walks under autograd, explainer_new.py:221-258): the
+// LDS-tiled kernels of tm_encoder_train_fwd up to attention.MLP's hidden layer (both dropouts of the attention
+// applied in the head), then the per-event tail of tm_encoder_pool_fwd.  F and the per-group std stay in
+// `workspace` for tm_encoder_pool_bwd.
+extern "C" int tm_encoder_pool_train_fwd(const tm_weights *w, const float *n_feat, const float *e_feat,
+                                         int32_t n_groups, int32_t B, int32_t W, const int32_t *node6,
+                                         const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
+                                         const float *cnt, const float *wgt, const uint8_t *drop, float drop_scale,
+                                         void *workspace, float *out, int64_t ld_out, void *stream) {
+    if (!w || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: bad arguments");
+    const int64_t n_walks = (int64_t)n_groups * B * W, n_events = (int64_t)n_groups * B;
+    if (n_events == 0) return TM_OK;
+    const EncW &P = w->P;
+    if (ld_out < P.hm)
+        return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: ld_out below the row width (hid_dim (+ 12))");
+    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !out)
+        return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: NULL pointer");
+    const size_t lds_g = gcn_lds(P);
+    if (lds_g > 160 * 1024 || head_lds(P, 16) > 160 * 1024 || P.h > 256)
+        return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_train_fwd: feature dims too large for LDS tile");
+    hipStream_t s = S_(stream);
+    float *F = reinterpret_cast<float *>(workspace);
+    float *stdv = F + n_walks * 3 * 2 * P.h;
+    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + pool_part_offset(w, n_walks));
+    hipEvent_t pe = nullptr;
+    if (n_walks > 0) {
+        pe = prof_begin(s);
+        if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
+        TM_CHECK_LAUNCH();
+        prof_end("std_kernel", s, pe);
+        const int64_t n_rows = n_walks * 3;
+        pe = prof_begin(s);
+        if (!launch_gcn_fwd_reg(P, w->node_zero, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, F, s))
+            launch_gcn(P, w->node_zero, n_rows, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
+        TM_CHECK_LAUNCH();
+        prof_end("gcn_kernel", s, pe);
+        pe = prof_begin(s);
+        head_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, head_lds(P, 16), s>>>(
+            P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, part, drop, drop_scale, wgt);
+        TM_CHECK_LAUNCH();
+        prof_end("head_pool_train_kernel", s, pe);
+    }
+    pe = prof_begin(s);
+    launch_pool_tail(P.a2, n_events, W, W, P.h, P.cat, part, wgt, cat, out, ld_out, s);
+    TM_CHECK_LAUNCH();
+    prof_end("pool_tail_kernel", s, pe);
     return TM_OK;
 }
 

@@ -294,32 +294,43 @@ struct HeadBwdOut {
 __host__ __device__ constexpr size_t head_bwd_lds_floats(int h, int hm, int TR) {
     return (size_t)TR * (4 * (2 * h + 8) + 2 * (h + 8) + 2 * (r16(hm) + 8));
 }
+// the POOL instance: no scoring MLP, so neither [TR][LDM] tile; dY2 takes the second [TR][LDH] one
+__host__ __device__ constexpr size_t head_pool_bwd_lds_floats(int h, int TR) {
+    return (size_t)TR * (4 * (2 * h + 8) + 2 * (h + 8));
+}
 
 // TR = 16 walks per workgroup (head_bwd_tr; the template also takes 32)
-template <int TR>
+// POOL (tm_encoder_pool_bwd, the backward of tm_encoder_pool_train_fwd): the recomputed forward stops at
+// attention.MLP's hidden layer H1d, d attention.MLP's output is wgt[walk] * d_emb[event of the walk][:h]
+// (d_emb rows ld_demb floats apart) instead of the scoring MLP's gradient, and the chain joins the common code at
+// d H1d; the six scoring-MLP buffers of `o` (dlogit, M2, dM2, M1d, dM1, X), imp, cat and d_imp are not touched
+template <int TR, bool POOL = false>
 __global__ void __launch_bounds__(256) head_bwd_kernel(EncW P, EncWT T, int64_t n_walks, int64_t walks_per_group,
                                                        int32_t W, const float *__restrict__ F,
                                                        const float *__restrict__ ts3, const double *__restrict__ cut,
                                                        const int32_t *__restrict__ cat, const float *__restrict__ stdv,
                                                        const uint8_t *__restrict__ drop, float dscale,
-                                                       const float *__restrict__ d_imp, HeadBwdOut o) {
+                                                       const float *__restrict__ d_imp, HeadBwdOut o,
+                                                       const float *__restrict__ wgt = nullptr,
+                                                       const float *__restrict__ d_emb = nullptr, int64_t ld_demb = 0) {
     static_assert(TR == 32 || TR == 16, "head_bwd_kernel: 16 or 32 walks per workgroup");
     constexpr int MT1 = TR / 16, MT2 = TR / 8;   // row tiles of TR and 2 TR rows
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int h = P.h, D2 = 2 * h, LD = D2 + 8, LDH = h + 8, KM = r16(P.hm), LDM = KM + 8;
-    const int dcols = drop_cols(h, P.hm), DM = DROP_H + h;
+    const int LDX = POOL ? LDH : LDM;   // row stride of Xb
+    [[maybe_unused]] const int dcols = drop_cols(h, P.hm), DM = DROP_H + h;
     float *Qb = smem;              // [2TR][LD] W2(F0 | F1)            -> dQ
     float *Wp = Qb + 2 * TR * LD;  // [TR][LD]  W1(F2)                 -> dP      (Wp..Ob: F0|F1 staging)
     float *Ob = Wp + TR * LD;      // [TR][LD]  F2 -> O                -> dO
     float *H1 = Ob + TR * LD;      // [TR][LDH] H1d                    -> dH1
-    float *Xb = H1 + TR * LDH;     // [TR][LDM] X                      -> dY2
-    float *M1 = Xb + TR * LDM;     // [TR][LDM] M1d                    -> dM1
-    float *M2 = M1 + TR * LDM;     // [TR][LDH] M2                     -> dM2
+    float *Xb = H1 + TR * LDH;     // [TR][LDM] X                      -> dY2     (POOL: [TR][LDH], dY2 alone)
+    [[maybe_unused]] float *M1 = Xb + TR * LDM;     // [TR][LDM] M1d                    -> dM1   (not in POOL)
+    [[maybe_unused]] float *M2 = M1 + TR * LDM;     // [TR][LDH] M2                     -> dM2   (not in POOL)
     __shared__ float s_mult[64], s_score[64], s_alpha[64], s_alphad[64], s_dsr[64], s_dl[32];
     __shared__ int32_t s_cat[32];
     const int64_t w0 = (int64_t)blockIdx.x * TR;
     const int tid = threadIdx.x;
-    const float kscale = drop ? dscale : 1.f;              // d(dropout(relu(z)))/dz where the output is > 0
+    [[maybe_unused]] const float kscale = drop ? dscale : 1.f;   // d(dropout(relu(z)))/dz where the output is > 0
     const float kscale_h = drop && P.tg ? dscale : 1.f;    // attention.MLP hidden: no Dropout in plain Attention
     auto valid = [&](int w) { return w0 + w < n_walks; };
     auto keep = [&](int w, int col) -> float {
@@ -346,7 +357,7 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(EncW P, EncWT T, int64_t 
         }
         s_mult[tid] = P.tg ? __fadd_rn(0.7f, __fmul_rn(0.3f, tw)) : 1.f;   // 1.0 - 0.3 + 0.3 * time_weight (:835-836)
     }
-    if (tid < TR) s_cat[tid] = valid(tid) ? cat[w0 + tid] : -1;
+    if (!POOL && tid < TR) s_cat[tid] = valid(tid) ? cat[w0 + tid] : -1;
     __syncthreads();
     gemm<MT2>(Tb, LD, P.w2, [&](int mt, int nt, floatx4 acc) {
         const int c = ecol(nt);
@@ -403,92 +414,107 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(EncW P, EncWT T, int64_t 
         }
     });
     __syncthreads();
-    gemm<MT1>(H1, LDH, P.a2, [&](int mt, int nt, floatx4 acc) {
-        const int c = ecol(nt);
-        for (int r = 0; r < 4; ++r) Xb[erow(mt, r) * LDM + c] = acc[r] + P.a2.b[c];
-    });
-    if (P.cat) {   // one-hot category after the attention output (:308-315)
-        for (int i = tid; i < TR * 16; i += blockDim.x) {
-            const int w = i >> 4, c = i & 15;
-            Xb[w * LDM + h + c] = (c < 12 && s_cat[w] == c) ? 1.f : 0.f;
-        }
-    }
-    __syncthreads();
-    for (int i = tid; i < TR * KM; i += blockDim.x) {
-        const int w = i / KM, c = i % KM;
-        if (valid(w)) o.X[(w0 + w) * KM + c] = Xb[w * LDM + c];
-    }
-    gemm<MT1>(Xb, LDM, P.m1, [&](int mt, int nt, floatx4 acc) {
-        const int c = ecol(nt);
-        for (int r = 0; r < 4; ++r) {
-            const int row = erow(mt, r);
-            const float v = c < P.m1.nout ? relu(acc[r] + P.m1.b[c]) * keep(row, DM + c) : 0.f;
-            M1[row * LDM + c] = v;
-            if (valid(row)) o.M1d[(w0 + row) * KM + c] = v;
-        }
-    });
-    __syncthreads();
-    gemm<MT1>(M1, LDM, P.m2, [&](int mt, int nt, floatx4 acc) {
-        const int c = ecol(nt);
-        for (int r = 0; r < 4; ++r) {
-            const int row = erow(mt, r);
-            const float v = relu(acc[r] + P.m2.b[c]);
-            M2[row * LDH + c] = v;
-            if (valid(row)) o.M2[(w0 + row) * h + c] = v;
-        }
-    });
-    __syncthreads();
-    {
-        const int w = tid >> 3, sub = tid & 7;
-        const int cend = w < TR ? h : 0;
-        float s = 0.f;
-        for (int c = sub; c < cend; c += 8) s += M2[w * LDH + c] * P.m3w[c];
-        s += __shfl_xor(s, 1, 8);
-        s += __shfl_xor(s, 2, 8);
-        s += __shfl_xor(s, 4, 8);
-        if (sub == 0 && w < TR) {
-            float dl = 0.f;
+    if constexpr (POOL) {
+        // pooled ending: the embedding is sum_w wgt_w (A2 h_w + b2), so d attention.MLP's output of walk w is
+        // wgt_w * d_emb[event(w)][:h] (histogram and base-embedding columns of the row are never read)
+        for (int i = tid; i < TR * h; i += blockDim.x) {
+            const int w = i / h, c = i % h;
+            float v = 0.f;
             if (valid(w)) {
-                const float y = 1.f / (1.f + expf(-(s + P.m3b[0])));
-                dl = d_imp[w0 + w] * (1.f - y) * y;   // sigmoid backward
-                if (o.imp) o.imp[w0 + w] = y;
-                o.dlogit[w0 + w] = dl;
+                v = wgt[w0 + w] * d_emb[((w0 + w) / W) * ld_demb + c];
+                o.dY2[(w0 + w) * h + c] = v;
             }
-            s_dl[w] = dl;
+            Xb[w * LDX + c] = v;
         }
-    }
-    __syncthreads();
-
-    // ---- backward through the MLP head
-    for (int i = tid; i < TR * h; i += blockDim.x) {
-        const int w = i / h, c = i % h;
-        const float v = M2[w * LDH + c] > 0.f ? s_dl[w] * P.m3w[c] : 0.f;
-        M2[w * LDH + c] = v;
-        if (valid(w)) o.dM2[(w0 + w) * h + c] = v;
-    }
-    __syncthreads();
-    gemm<MT1>(M2, LDH, T.m2T, [&](int mt, int nt, floatx4 acc) {   // d M1d = dM2 P3
-        const int c = ecol(nt);
-        for (int r = 0; r < 4; ++r) {
-            const int row = erow(mt, r);
-            const float v = (c < P.m1.nout && M1[row * LDM + c] > 0.f) ? acc[r] * kscale : 0.f;
-            M1[row * LDM + c] = v;
-            if (valid(row)) o.dM1[(w0 + row) * KM + c] = v;
+        __syncthreads();
+    } else {
+        gemm<MT1>(H1, LDH, P.a2, [&](int mt, int nt, floatx4 acc) {
+            const int c = ecol(nt);
+            for (int r = 0; r < 4; ++r) Xb[erow(mt, r) * LDM + c] = acc[r] + P.a2.b[c];
+        });
+        if (P.cat) {   // one-hot category after the attention output (:308-315)
+            for (int i = tid; i < TR * 16; i += blockDim.x) {
+                const int w = i >> 4, c = i & 15;
+                Xb[w * LDM + h + c] = (c < 12 && s_cat[w] == c) ? 1.f : 0.f;
+            }
         }
-    });
-    __syncthreads();
-    gemm<MT1>(M1, LDM, T.m1T, [&](int mt, int nt, floatx4 acc) {   // d X = dM1 P0; keep the attention part
-        const int c = ecol(nt);
-        if (c < h) {
+        __syncthreads();
+        for (int i = tid; i < TR * KM; i += blockDim.x) {
+            const int w = i / KM, c = i % KM;
+            if (valid(w)) o.X[(w0 + w) * KM + c] = Xb[w * LDM + c];
+        }
+        gemm<MT1>(Xb, LDM, P.m1, [&](int mt, int nt, floatx4 acc) {
+            const int c = ecol(nt);
             for (int r = 0; r < 4; ++r) {
                 const int row = erow(mt, r);
-                Xb[row * LDM + c] = acc[r];
-                if (valid(row)) o.dY2[(w0 + row) * h + c] = acc[r];
+                const float v = c < P.m1.nout ? relu(acc[r] + P.m1.b[c]) * keep(row, DM + c) : 0.f;
+                M1[row * LDM + c] = v;
+                if (valid(row)) o.M1d[(w0 + row) * KM + c] = v;
+            }
+        });
+        __syncthreads();
+        gemm<MT1>(M1, LDM, P.m2, [&](int mt, int nt, floatx4 acc) {
+            const int c = ecol(nt);
+            for (int r = 0; r < 4; ++r) {
+                const int row = erow(mt, r);
+                const float v = relu(acc[r] + P.m2.b[c]);
+                M2[row * LDH + c] = v;
+                if (valid(row)) o.M2[(w0 + row) * h + c] = v;
+            }
+        });
+        __syncthreads();
+        {
+            const int w = tid >> 3, sub = tid & 7;
+            const int cend = w < TR ? h : 0;
+            float s = 0.f;
+            for (int c = sub; c < cend; c += 8) s += M2[w * LDH + c] * P.m3w[c];
+            s += __shfl_xor(s, 1, 8);
+            s += __shfl_xor(s, 2, 8);
+            s += __shfl_xor(s, 4, 8);
+            if (sub == 0 && w < TR) {
+                float dl = 0.f;
+                if (valid(w)) {
+                    const float y = 1.f / (1.f + expf(-(s + P.m3b[0])));
+                    dl = d_imp[w0 + w] * (1.f - y) * y;   // sigmoid backward
+                    if (o.imp) o.imp[w0 + w] = y;
+                    o.dlogit[w0 + w] = dl;
+                }
+                s_dl[w] = dl;
             }
         }
-    });
-    __syncthreads();
-    gemm<MT1>(Xb, LDM, T.a2T, [&](int mt, int nt, floatx4 acc) {   // d H1d = dY2 A3
+        __syncthreads();
+
+        // ---- backward through the MLP head
+        for (int i = tid; i < TR * h; i += blockDim.x) {
+            const int w = i / h, c = i % h;
+            const float v = M2[w * LDH + c] > 0.f ? s_dl[w] * P.m3w[c] : 0.f;
+            M2[w * LDH + c] = v;
+            if (valid(w)) o.dM2[(w0 + w) * h + c] = v;
+        }
+        __syncthreads();
+        gemm<MT1>(M2, LDH, T.m2T, [&](int mt, int nt, floatx4 acc) {   // d M1d = dM2 P3
+            const int c = ecol(nt);
+            for (int r = 0; r < 4; ++r) {
+                const int row = erow(mt, r);
+                const float v = (c < P.m1.nout && M1[row * LDM + c] > 0.f) ? acc[r] * kscale : 0.f;
+                M1[row * LDM + c] = v;
+                if (valid(row)) o.dM1[(w0 + row) * KM + c] = v;
+            }
+        });
+        __syncthreads();
+        gemm<MT1>(M1, LDM, T.m1T, [&](int mt, int nt, floatx4 acc) {   // d X = dM1 P0; keep the attention part
+            const int c = ecol(nt);
+            if (c < h) {
+                for (int r = 0; r < 4; ++r) {
+                    const int row = erow(mt, r);
+                    Xb[row * LDM + c] = acc[r];
+                    if (valid(row)) o.dY2[(w0 + row) * h + c] = acc[r];
+                }
+            }
+        });
+        __syncthreads();
+    }
+    gemm<MT1>(Xb, LDX, T.a2T, [&](int mt, int nt, floatx4 acc) {   // d H1d = dY2 A3
         const int c = ecol(nt);
         for (int r = 0; r < 4; ++r) {
             const int row = erow(mt, r);
@@ -1710,6 +1736,42 @@ static bool gcn_bwd_uses_reg(const tm_weights *w) {
            w->T.evT.nt == 11 && w->T.evT.nq == 11 && P.ev.nq == nqe;
 }
 
+// the event_gcn backward launch of tm_encoder_bwd / tm_encoder_pool_bwd: io->dF down to lin_event and the time encoder
+static int launch_gcn_bwd(const tm_weights *w, int64_t n_walks, const float *n_feat, const float *e_feat,
+                          const int32_t *node6, const int32_t *eid3, const float *ts3, const float *cnt,
+                          const tm_encoder_grad_io *io, hipStream_t s) {
+    const EncW &P = w->P;
+    const int64_t n_rows = n_walks * 3;
+    GcnBwdOut go{io->ev, io->AB, io->H, io->dZ, io->dlev, io->g, io->dt};
+    hipEvent_t pe = prof_begin(s);
+    const int nqe = r16(P.kev) / 16;
+    // register-resident instance: hid_dim 64, 11 node-feature tiles (dn 161..176, a multiple of 4), lin_event
+    // with 11..14 K steps; the LDS-tiled kernel otherwise
+    const bool reg = gcn_bwd_uses_reg(w);
+    if (reg) {
+        const unsigned blocks = (unsigned)((n_rows + 63) / 64);
+#define TM_BWD_REG(Q)                                                                                              \
+        (w->node_zero ? gcn_bwd_reg_kernel<Q, true><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
+                                                                                 eid3, ts3, cnt, io->dF, go)          \
+                      : gcn_bwd_reg_kernel<Q, false><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
+                                                                                  eid3, ts3, cnt, io->dF, go))
+        if (nqe == 11) TM_BWD_REG(11);
+        else if (nqe == 12) TM_BWD_REG(12);
+        else if (nqe == 13) TM_BWD_REG(13);
+        else TM_BWD_REG(14);
+#undef TM_BWD_REG
+    } else if (w->node_zero) {
+        gcn_bwd_kernel<true><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, gcn_bwd_lds(P), s>>>(
+            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
+    } else {
+        gcn_bwd_kernel<false><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, gcn_bwd_lds(P), s>>>(
+            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
+    }
+    TM_CHECK_LAUNCH();
+    prof_end("gcn_bwd_kernel", s, pe);
+    return TM_OK;
+}
+
 extern "C" int tm_encoder_bwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
                               int32_t B, int32_t W, const int32_t *node6, const int32_t *eid3, const float *ts3,
                               const int32_t *cat, const double *cut, const float *cnt, const uint8_t *drop,
@@ -1739,35 +1801,41 @@ extern "C" int tm_encoder_bwd(const tm_weights *w, const float *n_feat, const fl
         P, w->T, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, drop, drop_scale, d_imp, ho);
     TM_CHECK_LAUNCH();
     prof_end("head_bwd_kernel", s, pe);
-    const int64_t n_rows = n_walks * 3;
-    GcnBwdOut go{io->ev, io->AB, io->H, io->dZ, io->dlev, io->g, io->dt};
-    pe = prof_begin(s);
-    const int nqe = r16(P.kev) / 16;
-    // register-resident instance: hid_dim 64, 11 node-feature tiles (dn 161..176, a multiple of 4), lin_event
-    // with 11..14 K steps; the LDS-tiled kernel otherwise
-    const bool reg = gcn_bwd_uses_reg(w);
-    if (reg) {
-        const unsigned blocks = (unsigned)((n_rows + 63) / 64);
-#define TM_BWD_REG(Q)                                                                                              \
-        (w->node_zero ? gcn_bwd_reg_kernel<Q, true><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
-                                                                                 eid3, ts3, cnt, io->dF, go)          \
-                      : gcn_bwd_reg_kernel<Q, false><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
-                                                                                  eid3, ts3, cnt, io->dF, go))
-        if (nqe == 11) TM_BWD_REG(11);
-        else if (nqe == 12) TM_BWD_REG(12);
-        else if (nqe == 13) TM_BWD_REG(13);
-        else TM_BWD_REG(14);
-#undef TM_BWD_REG
-    } else if (w->node_zero) {
-        gcn_bwd_kernel<true><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, lg, s>>>(
-            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
-    } else {
-        gcn_bwd_kernel<false><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, lg, s>>>(
-            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
-    }
+    return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
+}
+
+// Backward of tm_encoder_pool_train_fwd given d_emb = dL/d out (rows ld_demb floats apart; only the leading h
+// columns are read): head_bwd_kernel's POOL instance, then the event_gcn backward of tm_encoder_bwd.
+extern "C" int tm_encoder_pool_bwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
+                                   int32_t B, int32_t W, const int32_t *node6, const int32_t *eid3, const float *ts3,
+                                   const int32_t *cat, const double *cut, const float *cnt, const float *wgt,
+                                   const uint8_t *drop, float drop_scale, const void *workspace, const float *d_emb,
+                                   int64_t ld_demb, const tm_encoder_grad_io *io, void *stream) {
+    if (!w || !io || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_pool_bwd: bad arguments");
+    const int64_t n_walks = (int64_t)n_groups * B * W;
+    if (n_walks == 0) return TM_OK;
+    const EncW &P = w->P;
+    if (ld_demb < P.h) return fail(TM_E_ARG, "tm_encoder_pool_bwd: ld_demb below hid_dim");
+    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !d_emb)
+        return fail(TM_E_ARG, "tm_encoder_pool_bwd: NULL pointer");
+    if (!io->dY2 || !io->H1d || !io->dH1 || !io->O || !io->dP || !io->dQ || !io->dF || !io->ev || !io->AB || !io->H ||
+        !io->dZ || !io->dlev || !io->g || !io->dt)
+        return fail(TM_E_ARG, "tm_encoder_pool_bwd: NULL output buffer");
+    if (!w->tbuf) return fail(TM_E_ARG, "tm_encoder_pool_bwd: weights have no transposed packs");
+    const size_t lh = sizeof(float) * head_pool_bwd_lds_floats(P.h, 16);
+    if (P.h % 16 || !head_bwd_tr(P) || gcn_bwd_lds(P) > 160 * 1024)
+        return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_bwd: LDS budget exceeded");
+    hipStream_t s = S_(stream);
+    const float *F = reinterpret_cast<const float *>(workspace);
+    const float *stdv = F + n_walks * 3 * 2 * P.h;
+    HeadBwdOut ho{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, io->dY2, io->H1d, io->dH1, io->O,
+                  io->dP,  io->dQ,  io->dF};
+    hipEvent_t pe = prof_begin(s);
+    head_bwd_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, lh, s>>>(
+        P, w->T, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, drop, drop_scale, nullptr, ho, wgt, d_emb, ld_demb);
     TM_CHECK_LAUNCH();
-    prof_end("gcn_bwd_kernel", s, pe);
-    return TM_OK;
+    prof_end("head_pool_bwd_kernel", s, pe);
+    return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
 }
 
 // the register-resident event_gcn training forward (gcn_fwd_reg_kernel) for the dims it has an instance for:
@@ -1906,6 +1974,40 @@ extern "C" int tm_encoder_wgrad(const tm_weights *w, int32_t n_groups, int32_t B
                                     {grads[20], grads[21], 11, 1}};
     return run_wgrad(jobs, (int)(sizeof(jobs) / sizeof(jobs[0])), tgts, (int)(sizeof(tgts) / sizeof(tgts[0])),
                      S_(stream), "tm_encoder_wgrad");
+}
+
+// tm_encoder_wgrad without the scoring MLP (MLP.0 / .3 / .5 take no part in the pooled encoder): the same jobs
+extern "C" int tm_encoder_pool_wgrad(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W,
+                                     const tm_encoder_grad_io *io, const void *workspace, float *const *grads,
+                                     void *stream) {
+    if (!w || !io || !workspace || !grads || n_groups < 0 || B < 0 || W < 0)
+        return fail(TM_E_ARG, "tm_encoder_pool_wgrad: bad arguments");
+    for (int i = 0; i < TM_N_POOL_GRADS; ++i)
+        if (!grads[i]) return fail(TM_E_ARG, "tm_encoder_pool_wgrad: NULL gradient " + std::to_string(i));
+    const int64_t n64 = (int64_t)n_groups * B * W;
+    if (n64 * 3 * 2 > INT32_MAX) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_wgrad: too many walks per call");
+    const int n = (int)n64, R = 3 * n, h = w->h, h2 = 2 * h;
+    const int dn = w->dn, kev = w->P.kev, KE = r16(kev), DN = r16(dn);
+    const float *F = reinterpret_cast<const float *>(workspace);
+    const bool zn = w->node_zero;   // the zero-node row-pair form of tm_encoder_wgrad
+    const tm_wgrad_job zn0{io->dZ, io->AB, 2 * h, 2 * DN, h, dn, R}, zn2{io->dZ + h, io->H, 2 * h, 2 * h, h, h, R};
+    const tm_wgrad_job jobs[] = {
+        {io->dlev, io->ev, DN, KE, dn, kev, R},            // lin_event
+        zn ? zn0 : tm_wgrad_job{io->dZ, io->AB, h, DN, h, dn, 2 * R},   // event_conv.MLP.0
+        zn ? zn2 : tm_wgrad_job{io->dF, io->H, h, h, h, h, 2 * R},      // event_conv.MLP.2
+        {io->dP, F + 2 * h2, h2, 3 * h2, h2, h2, n},       // attention.W1 (x = F[:, 2])
+        {io->dQ, F, h2, 3 * h2, h2, h2, n},                // attention.W2, position 0
+        {io->dQ + (int64_t)n * h2, F + h2, h2, 3 * h2, h2, h2, n},   // position 1
+        {io->dH1, io->O, h, h2, h, h2, n},                 // attention.MLP.0
+        {io->dY2, io->H1d, h, h, h, h, n},                 // attention.MLP.3 (bias: sum_w wgt_w d_emb)
+        {io->g, io->dt, DN, 1, dn, 1, R},                  // time encoder: freq (x = dt), phase (ones)
+    };
+    const tm_wgrad_target tgts[] = {{grads[0], grads[1], 0, 1},   {grads[2], grads[3], 1, 1},
+                                    {grads[4], grads[5], 2, 1},   {grads[6], grads[7], 3, 1},
+                                    {grads[8], grads[9], 4, 2},   {grads[10], grads[11], 6, 1},
+                                    {grads[12], grads[13], 7, 1}, {grads[14], grads[15], 8, 1}};
+    return run_wgrad(jobs, (int)(sizeof(jobs) / sizeof(jobs[0])), tgts, (int)(sizeof(tgts) / sizeof(tgts[0])),
+                     S_(stream), "tm_encoder_pool_wgrad");
 }
 
 static int expl_hbits(int W) {

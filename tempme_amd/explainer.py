@@ -13,7 +13,9 @@ temporal-aware attention, MLP) and tm_edge_importance (dependency gate, walk->ed
 scatter-max, gather, Beta mean, mask).  Training-mode calls (dropout, Beta ``rsample``,
 gradients) run the HIP forward/backward kernels through autograd Functions
 (tm_encoder_train_fwd / tm_encoder_bwd / tm_encoder_wgrad, tm_explain_train_fwd / _bwd,
-tm_kl_loss); only Beta ``rsample`` and the padding mask are torch ops.
+tm_kl_loss); only Beta ``rsample`` and the padding mask are torch ops.  The motif-enhanced
+predictor (``enhance_predict_*``) runs tm_walk_importance and the pooled encoder: tm_encoder_pool_fwd in
+eval, tm_encoder_pool_train_fwd / _bwd / _wgrad when it trains; ``affinity_score`` stays torch ops.
 """
 import operator
 import os
@@ -1304,9 +1306,10 @@ class TempME(nn.Module):
             return out[:, :, :cols]
         return buf
 
-    def _enhance_sides_eval(self, sides, cut_time_l):
-        """The eval path of enhance_predict_*: sides = [(walks, edge_identify), ...] of one batch (same B and W)
-        as G groups -> [G, B, node_emd_dim] whose leading hid_dim (+ 12) columns hold the walk embeddings."""
+    def _enhance_stage(self, sides, cut_time_l):
+        """sides = [(walks, edge_identify), ...] of one batch (same B and W) as G groups of device tensors:
+        -> (node6, eid3, ts3, cat, cut [G,B], cnt, host, B, W); host: every input was a numpy array, checked here
+        against the embedding tables as the reference's lookups would."""
         dev = self._dev()
         G = len(sides)
         B, W = np.shape(sides[0][0][1])[0], np.shape(sides[0][0][1])[1]
@@ -1330,6 +1333,15 @@ class TempME(nn.Module):
             cu = _to(cut_time_l, dev, torch.float64)
             ei = torch.stack([_to(s[1], dev, torch.float32).reshape(B, W, 3, 3) for s in sides])
         cu = cu.reshape(1, B).expand(G, B).contiguous()
+        return n6, e3, t3, ct, cu, ei, host, B, W
+
+    def _enhance_sides_eval(self, sides, cut_time_l):
+        """The eval path of enhance_predict_*: sides = [(walks, edge_identify), ...] of one batch (same B and W)
+        as G groups -> [G, B, node_emd_dim] whose leading hid_dim (+ 12) columns hold the walk embeddings."""
+        dev = self._dev()
+        G = len(sides)
+        n_node = self.node_raw_embed.weight.shape[0]
+        n6, e3, t3, ct, cu, ei, host, B, W = self._enhance_stage(sides, cut_time_l)
         emb = torch.empty((G, B, self.node_emd_dim), dtype=torch.float32, device=dev)
         etab = self.dropin_edge_table()
         if etab is not None and not host and int(e3.max()) >= etab.shape[0]:
@@ -1339,6 +1351,150 @@ class TempME(nn.Module):
         self.enhance_groups(n6, e3, t3, ct, cu, ei, G, B, W, etab=etab, out=emb,
                             check=not host or self.node_degree.shape[0] < n_node)
         return emb
+
+    # ---- training (pooled encoder backward on the HIP kernels)
+    def _pool_params(self):
+        """The 16 tensors enhance_predict_walks reads (_encoder_params without MLP.0 / .3 / .5)."""
+        ws = self._weight_list()
+        return ws[:14] + ws[-2:]
+
+    def _enhance_drop_p(self):
+        """The p of the attention's two Dropouts as they act now (0 in eval mode and for the plain Attention, which
+        has none), or None when the two differ -- the kernels take one drop_scale.  The reference builds both with
+        TemporalAwareAttention's own default whatever TempME's dropout_p is (explainer_new.py:121, :769-780)."""
+        at = self.attention
+        if not isinstance(at, TemporalAwareAttention):
+            return 0.0
+        pa, ph = (float(m.p) if m.training else 0.0 for m in (at.dropout, at.MLP[2]))
+        return pa if pa == ph else None
+
+    def enhance_dropout_masks(self, n_walks):
+        """Keep-masks of the two dropouts enhance_predict_walks applies in training (alpha :839, attention.MLP
+        hidden :780) in dropout_masks' layout (the MLP-hidden columns are ignored), from torch's device RNG, or
+        (None, 1.0) when they are inactive."""
+        p = self._enhance_drop_p()
+        if p is None:
+            raise ValueError("enhance_dropout_masks: attention.dropout and attention.MLP[2] differ in p (or in "
+                             "training mode); pass keep-masks explicitly")
+        if p <= 0:
+            return None, 1.0
+        dev = self._dev()
+        return (torch.empty(n_walks, self.dropout_cols(), dtype=torch.uint8, device=dev).bernoulli_(1.0 - p),
+                1.0 / (1.0 - p))
+
+    def enhance_train_groups(self, node6, eid3, ts3, cat, cut, cnt, n_groups, B, W, drop=None, drop_scale=1.0,
+                             use_module_dropout=True, check=True):
+        """The differentiable twin of enhance_groups: enhance_predict_walks for n_groups reference calls at once
+        with gradients to the encoder's weights (tm_encoder_pool_train_fwd forward; tm_encoder_pool_bwd +
+        tm_encoder_pool_wgrad backward).  Inputs as forward_groups'; drop: uint8 keep-masks
+        [n_walks, dropout_cols()] (alpha 2 | attention.MLP hidden h | ignored), else the module's own dropouts
+        when they are active and use_module_dropout.  Returns [G, B, mlp_dim]: the hid_dim pooled columns carry
+        gradients, the histogram columns are constants; the walk weights get no gradient (times and degrees
+        only).  check: as walk_importance_groups."""
+        dev = self._dev()
+        if not self._hip_ok():
+            raise NotImplementedError("enhance_train_groups: no HIP training kernel instance for these dims")
+        if drop is None and use_module_dropout:
+            drop, drop_scale = self.enhance_dropout_masks(n_groups * B * W)
+        if drop is not None:
+            if drop.dtype != torch.uint8 or tuple(drop.shape) != (n_groups * B * W, self.dropout_cols()):
+                raise ValueError("enhance_train_groups: drop must be uint8 [%d, %d] (dropout_cols())"
+                                 % (n_groups * B * W, self.dropout_cols()))
+            drop = drop.to(dev).contiguous()
+        args = (node6.to(dev, torch.int32).contiguous(), eid3.to(dev, torch.int32).contiguous(),
+                ts3.to(dev, torch.float32).contiguous(), cat.to(dev, torch.int32).contiguous(),
+                cut.to(dev, torch.float64).contiguous(), cnt.to(dev, torch.float32).contiguous(),
+                int(n_groups), int(B), int(W))
+        wgt = self.walk_importance_groups(args[0], args[2], args[4], args[6], args[7], args[8], check=check)
+        return _PoolEncoderFn.apply(self, args, wgt, drop, float(drop_scale), *self._pool_params())
+
+    def _pool_train_fwd(self, args, wgt, drop, drop_scale):
+        node6, eid3, ts3, cat, cut, cnt, G, B, W = args
+        dev = self._dev()
+        nt, et = self.feature_tables()
+        w = self.packed_weights()
+        h, H = self.hid_dim, self._hid_packed()
+        drop = self._drop_packed(drop)
+        out = torch.empty((G, B, H + 12 if self.if_cat else H), dtype=torch.float32, device=dev)
+        ws = torch.empty(L.lib().tm_encoder_pool_train_workspace_bytes(w, G * B * W), dtype=torch.uint8, device=dev)
+        L.check(L.lib().tm_encoder_pool_train_fwd(w, L.ptr(nt), L.ptr(et), G, B, W, L.ptr(node6), L.ptr(eid3),
+                                                  L.ptr(ts3), L.ptr(cat), L.ptr(cut), L.ptr(cnt), L.ptr(wgt),
+                                                  L.ptr(drop), drop_scale, L.ptr(ws), L.ptr(out), int(out.shape[2]),
+                                                  L.stream_ptr(dev)), "enhance_predict_walks (training)")
+        if H != h:
+            out = out.index_select(2, self._pad_maps(dev)["cm"])    # [hidden units | histogram] of the padded row
+        return out, ws
+
+    def _pool_train_bwd(self, args, wgt, drop, drop_scale, ws, d_emb):
+        node6, eid3, ts3, cat, cut, cnt, G, B, W = args
+        dev = self._dev()
+        nt, et = self.feature_tables()
+        w = self.packed_weights()
+        n = G * B * W
+        R = 3 * n
+        drop = self._drop_packed(drop)
+        de, dn, hh, h = self.edge_dim, self.node_dim, self.hid_dim, self._hid_packed()   # h: the packed (padded) width
+        KE, DN = -(-(de + 3 + dn) // 16) * 16, -(-dn // 16) * 16
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        d_emb = d_emb.to(dev, torch.float32)
+        if h != hh:   # the padded units' columns: zero gradient
+            d = d_emb.new_zeros((G, B, h))
+            d[:, :, :hh] = d_emb[:, :, :hh]
+            d_emb = d
+        d_emb = d_emb.contiguous()
+        b = dict(dY2=e(n, h), H1d=e(n, h), dH1=e(n, h), O=e(n, 2 * h), dP=e(n, 2 * h), dQ=e(2, n, 2 * h),
+                 dF=e(n, 3, 2 * h), ev=e(R, KE), AB=e(R, 2, DN), H=e(R, 2, h), dZ=e(R, 2, h), dlev=e(R, DN), g=e(R, DN),
+                 dt=e(R))
+        io = L.EncoderGradIO(*[b[k].data_ptr() if k in b else None for k in L.GRAD_IO_FIELDS])
+        L.check(L.lib().tm_encoder_pool_bwd(w, L.ptr(nt), L.ptr(et), G, B, W, L.ptr(node6), L.ptr(eid3), L.ptr(ts3),
+                                            L.ptr(cat), L.ptr(cut), L.ptr(cnt), L.ptr(wgt), L.ptr(drop), drop_scale,
+                                            L.ptr(ws), L.ptr(d_emb), int(d_emb.shape[2]), L.C.byref(io),
+                                            L.stream_ptr(dev)), "enhance_predict_walks backward")
+        grads = [e(*s) for s in self._padded_shapes(_POOL_IDX)]
+        gp = (L.C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
+        L.check(L.lib().tm_encoder_pool_wgrad(w, G, B, W, L.C.byref(io), L.ptr(ws), gp, L.stream_ptr(dev)),
+                "enhance_predict_walks weight gradients")
+        return tuple(self._unpad_grads(grads, _POOL_IDX))
+
+    def _enhance_train(self):
+        """The HIP training path serves a module on a HIP device whose encoder parameters take gradients, when one
+        can be asked for (_needs_autograd: training mode, or grad mode on), for the dims the training kernels have
+        an instance for and one dropout p (_enhance_drop_p).  A frozen encoder keeps the paths it had."""
+        dev = self.node_raw_embed.weight.device if self.device is None else torch.device(self.device)
+        if dev.type != "cuda" or not self._needs_autograd():
+            return False
+        if not any(p.requires_grad for p in self._pool_params()) or self._enhance_drop_p() is None:
+            return False
+        return self._hip_ok()
+
+    def _enhance_sides_train(self, sides, cut_time_l):
+        """The training path of enhance_predict_*: sides of one shape as G groups -> [G, B, mlp_dim] through
+        _PoolEncoderFn, the module's dropouts drawn per group row (independent masks for every group)."""
+        dev = self._dev()
+        G = len(sides)
+        n_node, n_edge = self.node_raw_embed.weight.shape[0], self.edge_raw_embed.weight.shape[0]
+        n6, e3, t3, ct, cu, ei, host, B, W = self._enhance_stage(sides, cut_time_l)
+        if not host and n6.numel():
+            # device inputs: the embedding lookups' range check (one host sync); the kernels index the tables directly
+            lo = torch.stack([e3.min(), n6.min(), (n_edge - 1 - e3.max()).to(e3.dtype), (n_node - 1 - n6.max()).to(n6.dtype)])
+            if int(lo.min()) < 0:
+                raise IndexError("index out of range in self")
+        return self.enhance_train_groups(n6, e3, t3, ct, cu, ei, G, B, W,
+                                         check=not host or self.node_degree.shape[0] < n_node)
+
+    def _enhance_agg_train(self, ts_l_cut, sides, gats):
+        """enhance_predict_agg on the training path.  With active dropout four groups (src, tgt, src, bgd): the
+        reference encodes walks_src twice with separate draws (:205, :209); without, three, the src embedding
+        serving both pairs (its gradient sums).  affinity_score and the concatenations stay torch ops."""
+        active = (self._enhance_drop_p() or 0.0) > 0
+        s, t, b = sides
+        emb = self._enhance_sides_train([s, t, s, b] if active else [s, t, b], ts_l_cut)
+        g_s, g_t, g_b = (g.to(emb.device) for g in gats)
+        aff = self.affinity_score
+        e_s2, e_b = (emb[2], emb[3]) if active else (emb[0], emb[2])
+        pos = aff(torch.cat([emb[0], g_s], dim=-1), torch.cat([emb[1], g_t], dim=-1))
+        neg = aff(torch.cat([e_s2, g_s], dim=-1), torch.cat([e_b, g_b], dim=-1))
+        return pos, neg
 
     def compute_walk_importance(self, time_idx, node_idx, cut_time_l):
         """explainer_new.py:260-306 -> [bsz, n_walk]: on a HIP device one tm_walk_importance launch (fp64 group
@@ -1363,11 +1519,17 @@ class TempME(nn.Module):
     def enhance_predict_walks(self, walks, cut_time_l, edge_identify):
         """explainer_new.py:221-258 -> [bsz, hid_dim (+ 12)]."""
         if not self._enhance_eval():
+            if self._enhance_train():
+                return self._enhance_sides_train([(walks, edge_identify)], cut_time_l)[0]
             return self._enhance_walks_torch(walks, cut_time_l, edge_identify)
         return self._enhance_sides_eval([(walks, edge_identify)], cut_time_l)[0, :, :self.mlp_dim]
 
     def enhance_predict_pairs(self, walks_src, walks_tgt, cut_time_l, src_edge, tgt_edge):
-        """explainer_new.py:215-218 -> two [bsz, hid_dim (+ 12)]; eval: both sides in one launch."""
+        """explainer_new.py:215-218 -> two [bsz, hid_dim (+ 12)]; eval: both sides in one launch; training on a
+        HIP device: both sides as two groups of the pooled training path."""
+        if not self._enhance_eval() and np.shape(walks_src[1]) == np.shape(walks_tgt[1]) and self._enhance_train():
+            emb = self._enhance_sides_train([(walks_src, src_edge), (walks_tgt, tgt_edge)], cut_time_l)
+            return emb[0], emb[1]
         if not self._enhance_eval() or np.shape(walks_src[1]) != np.shape(walks_tgt[1]):
             return (self.enhance_predict_walks(walks_src, cut_time_l, src_edge),
                     self.enhance_predict_walks(walks_tgt, cut_time_l, tgt_edge))
@@ -1379,11 +1541,15 @@ class TempME(nn.Module):
         sides are three groups of one walk-importance and one pooled-encoder launch (the reference encodes
         walks_src twice with identical results, :205 / :209; here once), written into one [3, B, node_emd_dim]
         buffer beside the base embeddings; affinity_score runs in torch ops with fc1's src half computed once for
-        the positive and the negative pair.  Training, or gradients wanted: the torch formulation, with the
-        reference's two src encodings (dropout draws as the reference does)."""
+        the positive and the negative pair.  Training, or gradients wanted, on a HIP device with sides of one
+        shape: the pooled encoder's training kernels (_enhance_agg_train), affinity_score under autograd; else the
+        torch formulation, with the reference's two src encodings (dropout draws as the reference does)."""
         src_edge, tgt_edge, bgd_edge = edge_id_info
         gat_grad = torch.is_grad_enabled() and any(g.requires_grad for g in (src_gat, tgt_gat, bgd_gat))
         if not self._enhance_eval():
+            if np.shape(walks_src[1]) == np.shape(walks_tgt[1]) == np.shape(walks_bgd[1]) and self._enhance_train():
+                return self._enhance_agg_train(ts_l_cut, ((walks_src, src_edge), (walks_tgt, tgt_edge),
+                                                          (walks_bgd, bgd_edge)), (src_gat, tgt_gat, bgd_gat))
             return self._enhance_agg_torch(ts_l_cut, ((walks_src, src_edge), (walks_tgt, tgt_edge), (walks_bgd, bgd_edge)),
                                            (src_gat, tgt_gat, bgd_gat))
         if gat_grad or not (np.shape(walks_src[1]) == np.shape(walks_tgt[1]) == np.shape(walks_bgd[1])):
@@ -1628,6 +1794,25 @@ class _EncoderFn(torch.autograd.Function):
         return (None, None, None, None, *grads)
 
 
+class _PoolEncoderFn(torch.autograd.Function):
+    """enhance_predict_walks for G groups with its backward on the HIP kernels (tm_encoder_pool_train_fwd /
+    tm_encoder_pool_bwd / tm_encoder_pool_wgrad); params = TempME._pool_params() (MLP.0 / .3 / .5 take no part, as
+    in the reference's autograd graph)."""
+
+    @staticmethod
+    def forward(ctx, ex, args, wgt, drop, drop_scale, *params):
+        out, ws = ex._pool_train_fwd(args, wgt, drop, drop_scale)
+        ctx.ex, ctx.args, ctx.wgt, ctx.drop, ctx.drop_scale, ctx.ws = ex, args, wgt, drop, drop_scale, ws
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_emb):
+        grads = ctx.ex._pool_train_bwd(ctx.args, ctx.wgt, ctx.drop, ctx.drop_scale, ctx.ws, d_emb)
+        ctx.ws = None
+        return (None, None, None, None, None, *grads)
+
+
 class _EvalEncoderFn(torch.autograd.Function):
     """Eval-mode TempME.forward with gradients enabled: forward = the eval kernel's output (no dropout in
     eval, so it is the function the training kernels compute); backward recomputes through
@@ -1673,6 +1858,7 @@ def _C_APPLY(fn):
 _DP = torch.Tensor.data_ptr
 # tm_weights indices of TempME._encoder_params / _gate_params
 _ENC_IDX = tuple(range(20)) + (26, 27)
+_POOL_IDX = tuple(range(14)) + (26, 27)   # TempME._pool_params: tm_encoder_pool_wgrad's 16 (include/tempme.h)
 _GATE_IDX = tuple(range(20, 26)) + (26, 27)
 _VER = operator.attrgetter("_version")
 _RG = operator.attrgetter("requires_grad")

@@ -11,7 +11,13 @@ and the pooled kernel's executed FLOP per walk (bench.flops_model's executed ter
 products) with its fraction of the fp32 MFMA peak.  A second block repeats (a) at 24 batches (the bench's
 persistent-grid regime).
 
-    python tools/enhance_profile.py [--out FILE]
+--leg train measures the training step's half instead: enhance_predict_agg forward + backward in train mode
+(attention dropouts at p = 0.1) on the same B = 100 inputs, through the pooled encoder's training kernels
+(tm_encoder_pool_train_fwd / _bwd / _wgrad) and through _enhance_agg_torch + backward (the torch-op formulation,
+the only training path before those kernels) in the same process; tm_profile_* gives the library's kernels,
+--torch-kernels adds torch.profiler's device-kernel totals of the torch-op leg.
+
+    python tools/enhance_profile.py [--leg eval|train] [--torch-kernels] [--out FILE]
 """
 import argparse
 import json
@@ -55,9 +61,54 @@ def timed(fn, runs=RUNS):
             "kernels": {k: {"ms_per_run": v[0] / runs, "launches_per_run": v[1] / runs} for k, v in sorted(prof.items())}}
 
 
+def train_leg(ex, call, torch_call, gats, torch_kernels):
+    """Forward + backward of enhance_predict_agg in train mode: the HIP training path and the torch-op formulation."""
+    ex.train()
+    params = [p for p in ex.parameters() if p.requires_grad]
+
+    def step(fn):
+        def run():
+            for p in params:
+                p.grad = None
+            for g_ in gats:
+                g_.grad = None
+            pos, neg = fn()
+            (pos.sum() + neg.sum()).backward()
+        return run
+
+    def fwd(fn):
+        def run():
+            with torch.no_grad():
+                fn()
+        return run
+
+    assert ex._enhance_train(), "the HIP training path does not serve this module"
+    res = {"dropout_p": ex._enhance_drop_p(),
+           "hip_fwd_bwd": timed(step(call)), "torch_fwd_bwd": timed(step(torch_call)),
+           "hip_fwd_only": timed(fwd(call)), "torch_fwd_only": timed(fwd(torch_call))}
+    res["speedup_fwd_bwd"] = res["torch_fwd_bwd"]["median_ms"] / res["hip_fwd_bwd"]["median_ms"]
+    res["speedup_fwd_only"] = res["torch_fwd_only"]["median_ms"] / res["hip_fwd_only"]["median_ms"]
+    if torch_kernels:
+        from torch.profiler import ProfilerActivity, profile
+        for tag, fn in (("hip", step(call)), ("torch", step(torch_call))):
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                for _ in range(RUNS):
+                    fn()
+                torch.cuda.synchronize()
+            rows = sorted(prof.key_averages(), key=lambda e: -e.device_time_total)
+            res[tag + "_device_kernels"] = {
+                "total_ms_per_run": sum(e.device_time_total for e in rows) / RUNS / 1e3, "kernel_names": len(rows),
+                "top": [{"name": e.key[:100], "ms_per_run": e.device_time_total / RUNS / 1e3,
+                         "launches_per_run": e.count / RUNS} for e in rows[:12]]}
+    ex.eval()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--leg", choices=("eval", "train"), default="eval")
+    ap.add_argument("--torch-kernels", action="store_true")
     args = ap.parse_args()
     dev = L.require_device()
     g = enron_like(n_nodes=184, n_edges=125235)
@@ -81,7 +132,7 @@ def main():
     res["flop_per_walk"] = {"walk_kernel_executed": fm["walk_kernel_executed"], "walk_pool_kernel_executed": pool_flop}
     etab = ex.dropin_edge_table()
     w = ex.packed_weights()
-    for tag, E in (("headline_B100", B), ("persistent_24x100", 24 * B)):
+    for tag, E in ((("headline_B100", B), ("persistent_24x100", 24 * B)) if args.leg == "eval" else (("train_B100", B),)):
         ev = (to(src[:E], np.int32), to(dst[:E], np.int32), to(ts[:E], np.float64), to(eidx[:E], np.int32))
         buf = sample_events(f.graph, 1, tm.SPLIT_TEST, N, M, *ev, torch.arange(E, dtype=torch.int32, device=dev),
                             to(pool, np.int32))
@@ -94,6 +145,16 @@ def main():
         out = torch.empty(3, E, HID + 12, device=dev)
         imp = torch.empty(n_walks, device=dev)
         nt, et = ex.feature_tables()
+        if args.leg == "train":
+            h = lambda t: t.cpu().numpy().astype(np.float64)  # noqa: E731
+            sides = [((h(buf.node6[s]), h(buf.eid3[s]), h(buf.ts3[s]), h(buf.cat[s])[..., None], None), h(buf.cnt[s]))
+                     for s in range(3)]
+            gats = [torch.randn(E, 172, device=dev, requires_grad=True) for _ in range(3)]
+            cut_h = ts[:E].astype(np.float64)
+            res["agg_train"] = train_leg(
+                ex, lambda: ex.enhance_predict_agg(cut_h, sides[0][0], sides[1][0], sides[2][0], [s[1] for s in sides], *gats),
+                lambda: ex._enhance_agg_torch(cut_h, sides, gats), gats, args.torch_kernels)
+            break
 
         def pool_fwd():
             L.check(L.lib().tm_encoder_pool_fwd(w, L.ptr(nt), L.ptr(et), L.ptr(etab), 3, E, W, M, L.ptr(buf.node6),

@@ -743,6 +743,38 @@ int64_t tm_gm_packed_a_floats(int32_t n_out, int32_t k, int32_t n_mult, int32_t 
 /* W [n_out, k] row-major -> MFMA A-operand fragments (weights as the 16-output-row operand) */
 int tm_gm_pack_a(const float *w, int32_t n_out, int32_t k, int32_t n_mult, int32_t k_mult, float *packed, void *stream);
 
+/* ---------------------------------------------------------------- base GraphMixer training (learn_base.py)
+ * The training form of tm_gm_embed (model.train(), explain_weights = None, edge_attr = None, as
+ * learn_base.py:228-232 calls it): the same chain with the four dropouts of every mixer layer
+ * (FeedForwardNet: after the GELU and after the second Linear, token and channel FFN), and the gradient of
+ * every trainable embedding parameter.  The output layer and the MergeLayer score stay with the caller.
+ *
+ * `a` as for tm_gm_embed, except that every weight is the parameter itself, row-major and unpacked (proj_w
+ * [C, C+T], channel ffn.0 [HC, C], ffn.3 [C, HC]), and layer_table holds L x 14 pointers: tm_gm_embed's 12,
+ * then channel ffn.3 transposed ([HC, C]) and ffn.0 transposed ([C, HC]), plain row-major copies (read by the
+ * backward only).  a->ew or a->edge_attr set: TM_E_UNSUPPORTED.
+ *
+ * keep (nullable: no dropout) holds one byte per dropout element, 1 = kept, for each layer in order:
+ * tok_h [R][C][HT], tok_o [R][C][N], ch_h [R][N][HC], ch_o [R][N][C]; keep_scale = 1 / (1 - p).
+ *
+ * Dims: 1 <= N <= 32, 1 <= HT <= 16, C <= 256, T <= 256, 1 <= L <= 4 (tm_gm_train_ok).  The LDS tile of both
+ * kernels holds one layer, so it does not grow with L; layer inputs live in the workspace. */
+int tm_gm_train_ok(int32_t N, int32_t C, int32_t T, int32_t L, int32_t HT, int32_t HC);
+/* bytes of the workspace both calls share for R rows (-1 for dims tm_gm_train_ok rejects): the projection
+ * input [R N][C+T], every layer's input image [L][R N][C], d X [R N][C], then the weight-gradient operand
+ * images of one layer (reused layer by layer): four [R N][C], two [R N][HC], four [R C][32], two [R C][16] */
+int64_t tm_gm_train_workspace_bytes(int64_t R, int32_t N, int32_t C, int32_t T, int32_t L, int32_t HT, int32_t HC);
+/* forward: a->x_mean [R, C], a->node_out [R, D]; the workspace keeps what tm_gm_train_bwd needs */
+int tm_gm_train_fwd(const tm_gm_embed_args *a, const uint8_t *keep, float keep_scale, void *workspace, void *stream);
+/* backward from d_x_mean [R, C] (node_out has no trainable parameter behind it), with the same a, keep and
+ * workspace as the forward: grads = 2 + 12 L DEVICE pointers (the array itself on the host), written (not
+ * accumulated): projection_layer w [C, C+T], b [C], then per layer in the layer table's order token_norm w/b
+ * [N], token ffn.0 w [HT, N] / b, ffn.3 w [N, HT] / b, channel_norm w/b [C], channel ffn.0 w [HC, C] / b,
+ * ffn.3 w [C, HC] / b.  One activation-gradient launch per layer, last layer first, each followed by the
+ * layer's tm_wgrad jobs; deterministic (no float atomics). */
+int tm_gm_train_bwd(const tm_gm_embed_args *a, const uint8_t *keep, float keep_scale, void *workspace,
+                    const float *d_x_mean, float *const *grads, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

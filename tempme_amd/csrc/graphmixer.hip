@@ -29,6 +29,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "gm_common.h"
 
 namespace tmk {
 
@@ -49,8 +50,6 @@ struct GmArgs {
     float *x_mean, *node_out;
 };
 
-__host__ __device__ inline int32_t gm_r16(int32_t x) { return (x + 15) & ~15; }
-
 // row `off` of the device layer table as a global-address-space table of global pointers: loads through
 // generic pointers are FLAT loads, which also count on lgkmcnt (every later LDS wait waited for them)
 __device__ __forceinline__ gptr<const gptr<const float>> gm_layer(const float *const *lw, int off) {
@@ -67,15 +66,6 @@ __device__ __forceinline__ int gm_tid() {
     int t = threadIdx.x;
     asm volatile("" : "+v"(t));
     return t;
-}
-
-__device__ __forceinline__ float gm_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-
-// sum over the 64 lanes of a wave
-__device__ __forceinline__ float gm_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // The wave's output tiles nt0 + 4 i (i < ntw <= NTW) in one K loop: per K block the A fragments are read
@@ -908,10 +898,6 @@ struct GmBwd {
     const float *const *lw;     // [L][14]: tm_gm_embed's 12 (B-operand packs) + ffn.3^T, ffn.0^T packs
 };
 constexpr int GMB_LW = 14;
-
-__device__ __forceinline__ float gm_gelu_d(float x) {
-    return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
-}
 
 // token LayerNorm / FFN weights of one layer, staged in LDS
 struct GmTokW {

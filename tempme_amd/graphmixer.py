@@ -113,6 +113,37 @@ class _GmEmbedFn(torch.autograd.Function):
         return d_ew[:R].reshape(ctx.shape), None, None, None, None
 
 
+class _GmTrainFn(torch.autograd.Function):
+    """(x_mean, node_out) of tm_gm_train_fwd as a function of the embedding's parameters (projection_layer and
+    every mixer's 12 tensors, in the layer table's order): backward is tm_gm_train_bwd, one gradient per
+    parameter.  node_out depends on frozen tables only and takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, st, *params):
+        a, dev = st["args"], st["dev"]
+        R = a.R
+        x_mean = torch.empty(max(R, 1), a.C, dtype=torch.float32, device=dev)
+        node_out = torch.empty(max(R, 1), a.D, dtype=torch.float32, device=dev)
+        a.x_mean, a.node_out = L.ptr(x_mean), L.ptr(node_out)
+        L.check(L.lib().tm_gm_train_fwd(ctypes.byref(a), L.ptr(st["keep"]), st["keep_scale"], L.ptr(st["ws"]),
+                                        L.stream_ptr(dev)), "GraphMixer training forward")
+        ctx.st = st
+        ctx.shapes = [p.shape for p in params]
+        ctx.mark_non_differentiable(node_out)
+        return x_mean[:R], node_out[:R]
+
+    @staticmethod
+    def backward(ctx, d_xm, d_no):
+        st = ctx.st
+        a, dev = st["args"], st["dev"]
+        d_xm = (torch.zeros(max(a.R, 1), a.C, device=dev) if d_xm is None else d_xm).float().contiguous()
+        grads = [torch.empty(sh, dtype=torch.float32, device=dev) for sh in ctx.shapes]
+        arr = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
+        L.check(L.lib().tm_gm_train_bwd(ctypes.byref(a), L.ptr(st["keep"]), st["keep_scale"], L.ptr(st["ws"]),
+                                        L.ptr(d_xm), arr, L.stream_ptr(dev)), "GraphMixer training backward")
+        return (None, *grads)
+
+
 class GraphMixer(nn.Module):
     """graphmixer.py:53-101 constructor."""
 
@@ -327,11 +358,106 @@ class GraphMixer(nn.Module):
                             self.output_layer.bias.detach().to(dev))
         return F.linear(torch.cat([xm, no], dim=1), self.output_layer.weight.to(dev), self.output_layer.bias.to(dev))
 
+    # ------------------------------------------------------------------ HIP training path (tm_gm_train_*)
+    def train_on_hip(self, flag=True):
+        """Opt in to (or out of) the HIP training step: with the flag set, ``model.train()`` calls with
+        gradients enabled and neither explain_weights nor edge_attr run tm_gm_train_fwd / tm_gm_train_bwd, and
+        ``loss.backward()`` fills ``.grad`` on every parameter (learn_base.py).  Default off: the torch
+        formulation, as before."""
+        self._train_on_hip = bool(flag)
+        return self
+
+    def _train_hip_ok(self, explain_weight, edge_attr, N):
+        import os
+        if not getattr(self, "_train_on_hip", False) or not self.training or not torch.is_grad_enabled():
+            return False
+        if explain_weight is not None or edge_attr is not None or os.environ.get("TEMPME_GM_TORCH") == "1":
+            return False
+        if N != self.num_tokens or not self.num_layers:
+            return False
+        ht = int(self.mlp_mixers[0].token_feedforward.dim_expansion_factor * N)
+        return bool(L.lib().tm_gm_train_ok(N, self.num_channels, self.time_feat_dim, self.num_layers, ht,
+                                           int(self.channel_dim_expansion_factor * self.num_channels)))
+
+    def _gm_train_params(self):
+        """The embedding's trainable parameters in tm_gm_train_bwd's gradient order."""
+        ps = [self.projection_layer.weight, self.projection_layer.bias]
+        for m in self.mlp_mixers:
+            tf, cf = m.token_feedforward.ffn, m.channel_feedforward.ffn
+            ps += [m.token_norm.weight, m.token_norm.bias, tf[0].weight, tf[0].bias, tf[3].weight, tf[3].bias,
+                   m.channel_norm.weight, m.channel_norm.bias, cf[0].weight, cf[0].bias, cf[3].weight, cf[3].bias]
+        return ps
+
+    def keep_mask_bytes(self, R, N):
+        """Bytes of one step's dropout keep masks for R rows (tm_gm_train_fwd's layout, every layer)."""
+        C = self.num_channels
+        ht = int(self.mlp_mixers[0].token_feedforward.dim_expansion_factor * N)
+        hc = int(self.channel_dim_expansion_factor * C)
+        return self.num_layers * R * (C * ht + C * N + N * hc + N * C)
+
+    def draw_keep_masks(self, R, N, generator=None):
+        """One step's keep masks (1 = kept, probability 1 - dropout), drawn on the device in one allocation."""
+        dev = self._dev()
+        return torch.empty(self.keep_mask_bytes(R, N), dtype=torch.uint8, device=dev).bernoulli_(
+            1.0 - float(self.dropout), generator=generator)
+
+    def _embed_train_hip(self, dev, node_ids, cut, nid, eid, t):
+        R, N = nid.shape
+        params = self._gm_train_params()
+        for p in params:
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("GraphMixer.train_on_hip: parameters must be contiguous fp32 on the HIP device")
+        # the backward's two transposed operands per layer live in buffers of their own (stable pointers, so the
+        # layer table is built once) and are refreshed from the parameters every step
+        key = (dev, tuple(p.data_ptr() for p in params))
+        if getattr(self, "_gt_key", None) != key:
+            tr, rows = [], []
+            for l in range(self.num_layers):
+                lp = params[2 + 12 * l:14 + 12 * l]
+                w3t = torch.empty(lp[10].shape[1], lp[10].shape[0], dtype=torch.float32, device=dev)
+                w0t = torch.empty(lp[8].shape[1], lp[8].shape[0], dtype=torch.float32, device=dev)
+                tr += [(w3t, lp[10]), (w0t, lp[8])]
+                rows.append([x.data_ptr() for x in lp] + [w3t.data_ptr(), w0t.data_ptr()])
+            self._gt_state = dict(tr=tr, table=torch.tensor(rows, dtype=torch.int64).to(dev))
+            self._gt_key = key
+        st = self._gt_state
+        with torch.no_grad():
+            for buf, src in st["tr"]:
+                buf.copy_(src.t())
+        i32 = lambda x: x.to(dev, torch.int32).contiguous()  # noqa: E731
+        node, nid32, eid32 = i32(node_ids), i32(nid), i32(eid)
+        cut64 = cut.to(dev, torch.float64).reshape(-1).contiguous()
+        t64 = t.to(dev, torch.float64).contiguous()
+        tw = self.time_encoder.w.weight.detach().reshape(-1).to(dev, torch.float32).contiguous()
+        tb = self.time_encoder.w.bias.detach().to(dev, torch.float32).contiguous()
+        a = self._embed_args(dev, node, nid32, eid32, cut64, t64, None, None, params[0].detach(), params[1].detach(),
+                             tw, tb, st["table"])
+        p = float(self.dropout)
+        keep = getattr(self, "gm_keep_masks", None)
+        if keep is None and p > 0.0:
+            keep = self.draw_keep_masks(R, N)
+        if keep is not None:
+            if keep.dtype != torch.uint8 or keep.numel() != self.keep_mask_bytes(R, N) or keep.device != dev:
+                raise ValueError("GraphMixer.gm_keep_masks: expected keep_mask_bytes(R, N) uint8 values on the device")
+            keep = keep.contiguous()
+        nbytes = int(L.lib().tm_gm_train_workspace_bytes(R, a.N, a.C, a.T, a.L, a.HT, a.HC))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        state = dict(args=a, dev=dev, keep=keep, keep_scale=1.0 / (1.0 - p) if p > 0.0 else 1.0, ws=ws,
+                     hold=(node, nid32, eid32, cut64, t64, tw, tb, st, self._tables(dev)))
+        xm, no = _GmTrainFn.apply(state, *params)
+        self._gm_train_key = (R, N, keep is not None)   # marker: the HIP training path ran
+        return self.output_layer(torch.cat([xm, no], dim=1))
+
     def node_embeddings(self, node_ids, cut_time, nid, eid, times, explain_weight=None, edge_attr=None):
         """compute_node_temporal_embeddings (graphmixer.py:142-193) for R rows at once:
         node_ids [R], cut_time [R] (f64), nid/eid/times [R, N] (hop-1 records), explain_weight [R, N]."""
         dev = self._dev()
         N0 = np.shape(nid)[-1]
+        if self._train_hip_ok(explain_weight, edge_attr, N0):
+            return self._embed_train_hip(dev, _as_dev(node_ids, dev, torch.long).reshape(-1),
+                                         _as_dev(cut_time, dev, torch.float64).reshape(-1),
+                                         _as_dev(nid, dev, torch.long), _as_dev(eid, dev, torch.long),
+                                         _as_dev(times, dev, torch.float64))
         mode = self._hip_mode(explain_weight, N0)
         if mode is not None:
             return self._embed_hip(dev, _as_dev(node_ids, dev, torch.long).reshape(-1),

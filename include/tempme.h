@@ -474,6 +474,12 @@ int tm_stage_cast(const tm_stage_job *jobs, int32_t n_jobs, void *stream);
 int tm_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
                  float beta2, float eps, float weight_decay, float grad_scale, float *step, uint32_t *done,
                  int32_t advance, void *stream);
+/* tm_adam_step gated by a device flag: `*gate == 0` leaves param / exp_avg / exp_avg_sq of the span untouched (the
+ * step count still advances when advance != 0).  Data-parallel training: a span this rank did not reach is updated
+ * iff some rank reached it, which the all-reduced flag says without a host synchronisation. */
+int tm_adam_step_gated(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, float grad_scale, float *step,
+                       uint32_t *done, int32_t advance, const float *gate, void *stream);
 /* Up to 32 fp32 copies in one launch (dst[0:n) = src[0:n) per job): the parameters' gradients, as autograd
  * produced them, into the flat bucket tm_adam_step and the gradient all-reduce read. */
 typedef struct tm_copy_job {

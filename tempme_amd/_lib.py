@@ -44,7 +44,7 @@ EXPORTS = (
     "tm_explain_train_fwd", "tm_explain_train_fwd_pad", "tm_explain_train_bwd", "tm_kl_loss", "tm_edge_importance", "tm_edge_gate_table",
     "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_tgat_attn_fwd", "tm_tgat_attn_bwd", "tm_tgat_merge_fwd", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_gm_train_ok", "tm_gm_train_workspace_bytes", "tm_gm_train_fwd", "tm_gm_train_bwd", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
     "tm_mask_least_important", "tm_profile_enable", "tm_profile_sync", "tm_profile_entry",
-    "tm_beta_params", "tm_beta_rsample_bwd", "tm_adam_step", "tm_copy_many", "tm_host_register", "tm_host_unregister",
+    "tm_beta_params", "tm_beta_rsample_bwd", "tm_adam_step", "tm_adam_step_gated", "tm_copy_many", "tm_host_register", "tm_host_unregister",
     "tm_stage_cast",
 )
 
@@ -236,6 +236,7 @@ def _sig(L):
     L.tm_beta_params.argtypes = [vp, i64, vp, vp, vp]
     f32 = C.c_float
     L.tm_adam_step.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, i32, vp]
+    L.tm_adam_step_gated.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, i32, vp, vp]
     L.tm_copy_many.argtypes = [C.POINTER(CopyJob), i32, vp]
     L.tm_host_register.argtypes = [vp, i64, C.POINTER(vp)]
     L.tm_host_unregister.argtypes = [vp]

@@ -26,16 +26,20 @@ struct AdamArgs {
     uint32_t *done;       // device: completion counter, 0 between launches
     int64_t head;         // elements before the first 16-byte-aligned one (the four buffers share the offset)
     int advance;          // this launch advances the step count (the last of a step's launches)
+    const float *gate;    // device, or NULL: *gate == 0 leaves the span untouched (the step count still advances)
 };
 
 __device__ __forceinline__ void adam_elem(float &p, float g, float &m, float &v, const AdamArgs &a, float step_size,
                                           float bc2_sqrt) {
     g *= a.grad_scale;
     if (a.weight_decay != 0.f) g = __builtin_fmaf(a.weight_decay, p, g);
-    m = m + (1.f - a.beta1) * (g - m);                    // torch.lerp with weight < 0.5
+    // the fused multiply-adds are spelled out: left to the compiler's contraction, the float4 loop fused m's and the
+    // scalar head / tail path did not, so an element's bits depended on where its span began (a step split into
+    // runs differed from the same step in one launch)
+    m = __builtin_fmaf(1.f - a.beta1, g - m, m);          // torch.lerp with weight < 0.5
     v = __builtin_fmaf((1.f - a.beta2) * g, g, v * a.beta2);
     const float denom = sqrtf(v) / bc2_sqrt + a.eps;
-    p = p + (-step_size) * (m / denom);
+    p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
 __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a) {
@@ -49,7 +53,9 @@ __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a) {
     float4 *m4 = reinterpret_cast<float4 *>(a.m + h);
     float4 *v4 = reinterpret_cast<float4 *>(a.v + h);
     const float4 *g4 = reinterpret_cast<const float4 *>(a.g + h);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    // a gated span no rank reached stays put (uniform over the grid: every thread reads the same flag)
+    const bool live = !a.gate || *a.gate != 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; live && i < n4; i += stride) {
         float4 p = p4[i], m = m4[i], v = v4[i];
         const float4 g = g4[i];
         adam_elem(p.x, g.x, m.x, v.x, a, step_size, bc2_sqrt);
@@ -62,7 +68,7 @@ __global__ void __launch_bounds__(256) adam_kernel(AdamArgs a) {
     }
     // the unaligned head and the tail after the last float4 (at most 3 + 3 elements)
     const int64_t tail = (a.n - h) & 3;
-    if (blockIdx.x == 0 && threadIdx.x < h + tail) {
+    if (live && blockIdx.x == 0 && threadIdx.x < h + tail) {
         const int64_t i = threadIdx.x < h ? (int64_t)threadIdx.x : h + (n4 << 2) + (threadIdx.x - h);
         float p = a.p[i], m = a.m[i], v = a.v[i];
         adam_elem(p, a.g[i], m, v, a, step_size, bc2_sqrt);
@@ -121,9 +127,9 @@ extern "C" int tm_copy_many(const tm_copy_job *jobs, int32_t n_jobs, void *strea
     return TM_OK;
 }
 
-extern "C" int tm_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
-                            float beta1, float beta2, float eps, float weight_decay, float grad_scale, float *step,
-                            uint32_t *done, int32_t advance, void *stream) {
+static int adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
+                     float beta1, float beta2, float eps, float weight_decay, float grad_scale, float *step,
+                     uint32_t *done, int32_t advance, const float *gate, void *stream) {
     if (n < 0 || !(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f))
         return fail(TM_E_ARG, "tm_adam_step: bad arguments");
     if (n == 0) return TM_OK;
@@ -134,7 +140,7 @@ extern "C" int tm_adam_step(float *param, const float *grad, float *exp_avg, flo
             return fail(TM_E_ARG, "tm_adam_step: the four buffers must share their offset within 16 bytes");
     const int64_t head = std::min<int64_t>(n, (int64_t)((16 - mis) & 15) / 4);
     AdamArgs a{param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step, done,
-               head, advance ? 1 : 0};
+               head, advance ? 1 : 0, gate};
     const int64_t n4 = (n - head) >> 2;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n4 + 255) / 256, 2048));
     hipEvent_t pe = prof_begin((hipStream_t)stream);
@@ -142,4 +148,21 @@ extern "C" int tm_adam_step(float *param, const float *grad, float *exp_avg, flo
     TM_CHECK_LAUNCH();
     prof_end("adam_kernel", (hipStream_t)stream, pe);
     return TM_OK;
+}
+
+extern "C" int tm_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
+                            float beta1, float beta2, float eps, float weight_decay, float grad_scale, float *step,
+                            uint32_t *done, int32_t advance, void *stream) {
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step, done,
+                     advance, nullptr, stream);
+}
+
+// tm_adam_step over a span whose update depends on a device flag (data-parallel training: a parameter this rank did
+// not reach is updated iff some rank reached it, which only the all-reduced flag knows)
+extern "C" int tm_adam_step_gated(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                                  float *step, uint32_t *done, int32_t advance, const float *gate, void *stream) {
+    if (!gate) return fail(TM_E_ARG, "tm_adam_step_gated: NULL gate");
+    return adam_step(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, grad_scale, step, done,
+                     advance, gate, stream);
 }

@@ -12,9 +12,21 @@ on ``flat_grad`` itself.  The step count lives on the device, so the step is cap
 (train.GraphedTrainStep).
 
 Semantics = torch.optim.Adam with amsgrad=False, maximize=False (the reference's arguments).  torch skips a parameter
-whose ``.grad`` is None (nothing reached it in backward); a post-accumulate-grad hook records which parameters
-autograd reached since ``zero_grad`` and the step updates only their spans (one launch when every parameter was
-reached, the common case; a launch per contiguous run otherwise).
+whose ``.grad`` is None (nothing reached it in backward) and updates every other one, a zero gradient included
+(``zero_grad(set_to_none=False)``: the moments decay, weight decay applies).  So a parameter is *reached* iff its
+``.grad`` is not None when ``step()`` runs, and the step updates the reached spans only (one launch when every
+parameter was reached, the common case; a launch per contiguous run otherwise).
+
+Data parallel (``reduce_buffer()``, called by train.GradAllReduce(bucket=opt).start()): the buffer that is all-reduced
+is the gradient bucket followed by one reach flag per parameter.  Before the collective the spans this rank did not
+reach are zeroed (never a stale gradient of an earlier step) and its flags say which it reached; after it a flag is
+non-zero iff SOME rank reached the parameter.  The next ``step()`` then updates the union: this rank's reached runs as
+above, and each span it did not reach through ``tm_adam_step_gated`` on that parameter's flag -- the kernel leaves a
+span no rank reached untouched, as torch leaves it (no weight decay, no moment decay).  Every rank thus applies the
+same update to the same spans, with no host synchronisation (the flags never leave the device).  A rank that reached
+everything launches exactly what it launches alone, plus one fill of the flags.  Without ``reduce_buffer()`` (one GPU)
+nothing of this runs.
+
 One step count is shared by the bucket, as torch's per-parameter counts are equal when the same parameters receive
 gradients every step (the reference's training loop).
 """
@@ -45,7 +57,11 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("FusedAdam: a parameter is listed twice")
         n = sum(p.numel() for p in ps)
         self.flat_param = torch.empty(n, dtype=torch.float32, device=dev)
-        self.flat_grad = torch.zeros(n, dtype=torch.float32, device=dev)
+        # the gradients, then one reach flag per parameter (all-reduced together, reduce_buffer)
+        self._grad_buf = torch.zeros(n + len(ps), dtype=torch.float32, device=dev)
+        self.flat_grad = self._grad_buf[:n]
+        self.reach_flags = self._grad_buf[n:]
+        self._shared = False      # reduce_buffer() ran since the last step: the step updates the ranks' union
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
         self.step_t = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -59,10 +75,6 @@ class FusedAdam(torch.optim.Optimizer):
                 self._spans.append((p, off, k))
                 off += k
         self._params = [p for p, _, _ in self._spans]
-        self._index = {id(p): i for i, p in enumerate(self._params)}
-        self._reached = set()
-        for i, p in enumerate(self._params):
-            p.register_post_accumulate_grad_hook(lambda _p, i=i: self._reached.add(i))
         self._bind()
 
     def _bind(self):
@@ -84,7 +96,6 @@ class FusedAdam(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=True):
         """``set_to_none`` (torch's default): every ``.grad`` None, so backward hands each parameter autograd's own
         gradient tensor (no accumulation kernel); else one fill of the bucket with the views bound."""
-        self._reached.clear()
         if set_to_none:
             for p in self._params:
                 p.grad = None
@@ -120,37 +131,68 @@ class FusedAdam(torch.optim.Optimizer):
             p.grad = self.flat_grad[off:off + k].view_as(p)
         return rebind
 
+    def _unreached_runs(self):
+        """[(first parameter, one past the last, first element, one past the last)] of the contiguous runs of
+        parameters whose ``.grad`` is None."""
+        runs, start = [], None
+        for i, (p, off, k) in enumerate(self._spans + [(None, self.flat_param.numel(), 0)]):
+            miss = p is not None and p.grad is None
+            if miss and start is None:
+                start = (i, off)
+            elif not miss and start is not None:
+                runs.append((start[0], i, start[1], off))
+                start = None
+        return runs
+
+    @torch.no_grad()
+    def reduce_buffer(self):
+        """The buffer a data-parallel all-reduce (SUM or mean) runs on, in place: the gradient bucket and the reach
+        flags behind it.  Gathers the gradients (``sync_grads``), zeroes the spans this rank did not reach and sets its
+        flags; the next ``step()`` updates the union of the ranks' reached spans (module docstring)."""
+        self.sync_grads()
+        self.reach_flags.fill_(1.0)
+        for i, j, a, b in self._unreached_runs():
+            self.flat_grad[a:b].zero_()
+            self.reach_flags[i:j].zero_()
+        self._shared = True
+        return self._grad_buf
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        # the reached parameters' gradients into the bucket (a .grad set by the caller counts as reached)
-        for p, g0 in [(p, p.grad) for p, _, _ in self._spans]:
-            if g0 is not None and g0.data_ptr() != self.flat_grad.data_ptr() + 4 * self._spans[self._index[id(p)]][1]:
-                self._reached.add(self._index[id(p)])
+        # the reached parameters' gradients into the bucket (reached = .grad is not None: autograd's, the caller's, or
+        # the zero view zero_grad(set_to_none=False) left)
         self.sync_grads()
         for p, off, k in self._spans:
             if p.data_ptr() != self.flat_param[off:].data_ptr():
                 raise RuntimeError("FusedAdam: a parameter was rebound away from the flat bucket")
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        # contiguous runs of the parameters autograd reached (torch.optim.Adam skips the others)
-        runs, start = [], None
-        for i, (p, off, k) in enumerate(self._spans + [(None, self.flat_param.numel(), 0)]):
-            hit = i < len(self._spans) and i in self._reached
-            if hit and start is None:
-                start = off
-            elif not hit and start is not None:
-                runs.append((start, off))
-                start = None
-        fn, st = L.lib().tm_adam_step, L.stream_ptr(self.flat_param.device)
-        for r, (a, b) in enumerate(runs):
-            L.check(fn(self.flat_param.data_ptr() + 4 * a, self.flat_grad.data_ptr() + 4 * a,
-                       self.exp_avg.data_ptr() + 4 * a, self.exp_avg_sq.data_ptr() + 4 * a, b - a, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
-                       float(g["weight_decay"]), 1.0, L.ptr(self.step_t), L.ptr(self._done), int(r + 1 == len(runs)),
-                       st), "FusedAdam.step")
+        # contiguous runs of the reached parameters (torch.optim.Adam skips the others); after reduce_buffer() also
+        # every span this rank did not reach, gated on its all-reduced flag (updated iff some rank reached it)
+        runs, at = [], 0
+        for i, j, a, b in self._unreached_runs():
+            if a > at:
+                runs.append((at, a, None))
+            if self._shared:
+                runs += [(off, off + k, i + q) for q, (_, off, k) in enumerate(self._spans[i:j])]
+            at = b
+        if at < self.flat_param.numel():
+            runs.append((at, self.flat_param.numel(), None))
+        self._shared = False
+        lib, st = L.lib(), L.stream_ptr(self.flat_param.device)
+        for r, (a, b, flag) in enumerate(runs):
+            args = (self.flat_param.data_ptr() + 4 * a, self.flat_grad.data_ptr() + 4 * a,
+                    self.exp_avg.data_ptr() + 4 * a, self.exp_avg_sq.data_ptr() + 4 * a, b - a, float(g["lr"]),
+                    float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), 1.0, L.ptr(self.step_t),
+                    L.ptr(self._done), int(r + 1 == len(runs)))
+            if flag is None:
+                L.check(lib.tm_adam_step(*args, st), "FusedAdam.step")
+            else:
+                L.check(lib.tm_adam_step_gated(*args, self.reach_flags.data_ptr() + 4 * flag, st), "FusedAdam.step")
         # the kernel wrote the parameters behind autograd's back: bump their version counters as torch's in-place
         # update would, so caches keyed on them (the explainer's packed weights) see the change
         increment_version(self._params)

@@ -148,8 +148,15 @@ class GradAllReduce:
 
     def __init__(self, module, group=None, force=False, bucket=None):
         """``bucket``: the module's optimizer when it keeps the gradients in one flat buffer (optim.FusedAdam):
-        ``start`` gathers them there (``bucket.sync_grads()``, one launch per 32 parameters) and the all-reduce runs
-        on ``bucket.flat_grad`` in place -- no per-parameter packing copies before the collective or after it."""
+        ``start`` gathers them there (one launch per 32 parameters) and the all-reduce runs on the bucket in place --
+        no per-parameter packing copies before the collective or after it.  A bucket with ``reduce_buffer()``
+        (FusedAdam) hands over the gradients followed by one reach flag per parameter: spans this rank did not reach
+        go into the collective as zeros (never as an earlier step's gradient), and the reduced flags tell every
+        rank's ``bucket.step()`` which spans SOME rank reached -- it updates exactly those, so the replicas stay
+        identical when the ranks reach different parameters, and a parameter no rank reached stays put as under
+        torch.optim.Adam.  The flags stay on the device (no host synchronisation); in a group of one without
+        ``force`` none of this runs.  A bucket without it (``flat_grad`` and ``sync_grads()`` only) keeps its
+        gradients current itself."""
         self.module, self.group = module, group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.force = bool(force) and dist.is_initialized()
@@ -163,8 +170,12 @@ class GradAllReduce:
         if self.world == 1 and not self.force:
             return
         if self.flat_grad is not None:
-            self.bucket.sync_grads()
-            self._flat, self._grads = self.flat_grad, None
+            if hasattr(self.bucket, "reduce_buffer"):
+                self._flat = self.bucket.reduce_buffer()
+            else:
+                self.bucket.sync_grads()
+                self._flat = self.flat_grad
+            self._grads = None
             self._work = dist.all_reduce(self._flat, op=dist.ReduceOp.SUM, group=self.group, async_op=True)
             return
         grads = [p.grad for p in self.module.parameters() if p.grad is not None]

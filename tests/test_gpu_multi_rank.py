@@ -8,6 +8,8 @@
   GradAllReduce over the device gradient buffers equals the average of the ranks' local gradients, which
   equals one process's average of the two batches' gradients, and the replicas stay identical through
   run_steps (the all-reduce overlapped with the next batch's preparation).
+* The ranks reach different parameters: FusedAdam's bucket goes into the collective with zeros in the spans this rank
+  did not reach, and every rank updates the union of the reached spans (flags all-reduced with the bucket).
 
 The processes are spawned (no fork or exec after the parent touched the GPU; the parent never does)."""
 import os
@@ -223,3 +225,75 @@ def _train_worker(rank, world, port, q):
 
 def test_grad_all_reduce_on_device_equals_average():
     _spawn(_train_worker)
+
+
+# ------------------------------------------------------------------ FusedAdam's bucket, partly reached
+def _partial_net(dtype=torch.float32):
+    torch.manual_seed(21)
+    net = torch.nn.ModuleDict(dict(A=torch.nn.Linear(5, 7), X=torch.nn.Linear(7, 3), Y=torch.nn.Linear(3, 3)))
+    return net.to(dtype)
+
+
+def _partial_loss(net, step, rank, dev, dtype=torch.float32):
+    """Step 0: both ranks reach A and X (different inputs).  Step 1: rank 0 reaches A and X, rank 1 only A.  Y:
+    never."""
+    x = torch.randn(16, 5, generator=torch.Generator().manual_seed(10 * step + rank)).to(dev, dtype)
+    h = net["A"](x)
+    if step == 1 and rank == 1:
+        return h.pow(2).mean()
+    return net["X"](torch.relu(h)).pow(2).mean()
+
+
+def _partial_reach_worker(rank, world, port, q):
+    """A real FusedAdam behind GradAllReduce(bucket=opt), weight decay on: after every step the replicas are bitwise
+    equal and match one process's torch.optim.Adam (fp64) on the mean of the ranks' losses; a span one rank did not
+    reach takes the other rank's gradient (not a stale one), the layer no rank reached does not move."""
+    try:
+        dev = _init(rank, world, port)
+        from tempme_amd.optim import FusedAdam
+        from tempme_amd.train import GradAllReduce
+        net = _partial_net().to(dev)
+        opt = FusedAdam(net.parameters(), lr=1e-2, weight_decay=1e-2)
+        sync = GradAllReduce(net, bucket=opt)
+        y0 = [p.detach().clone() for p in net["Y"].parameters()]
+        flats = []
+        for step in range(2):
+            opt.zero_grad()
+            _partial_loss(net, step, rank, dev).backward()
+            sync.start()
+            sync.finish()
+            opt.step()
+            got = [torch.empty_like(opt.flat_param) for _ in range(world)]
+            dist.all_gather(got, opt.flat_param)
+            flats.append([g.cpu() for g in got])
+        err = None
+        try:
+            assert float(opt.step_t.item()) == 2.0
+            for a, b in zip(y0, net["Y"].parameters()):
+                assert torch.equal(a, b), "the layer no rank reached moved"
+            ref = _partial_net(torch.float64)
+            ropt = torch.optim.Adam(ref.parameters(), lr=1e-2, weight_decay=1e-2)
+            for step in range(2):
+                ropt.zero_grad()
+                (sum(_partial_loss(ref, step, r, "cpu", torch.float64) for r in range(world)) / world).backward()
+                ropt.step()
+                assert torch.equal(flats[step][0], flats[step][1]), f"step {step + 1}: the replicas differ"
+                want = torch.cat([p.detach().reshape(-1) for p in ref.parameters()]).float()
+                torch.testing.assert_close(flats[step][rank], want, rtol=1e-5, atol=1e-6, msg=f"step {step + 1}")
+        except AssertionError as exc:
+            err = repr(exc)
+        errs = [None] * world
+        dist.all_gather_object(errs, err)
+        if rank == 0:
+            q.put("ok" if not any(errs) else repr(errs))
+        dist.barrier()
+    except Exception as exc:
+        q.put(repr(exc))
+        raise
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def test_fused_adam_bucket_partly_reached_two_ranks():
+    _spawn(_partial_reach_worker)

@@ -667,6 +667,29 @@ int tm_tgat_attn_fwd(const tm_tgat_attn *a, float *z, float *stats, void *stream
 int tm_tgat_attn_bwd(const tm_tgat_attn *a, const float *stats, const float *gz, float *d_ew_parts, float *d_node,
                      float *d_qf, void *stream);
 
+/* Training pair of the same attention pass (learn_base.py for --base_type tgat): the attention dropout of
+ * ScaledDotProductAttention (:74-78: after the softmax, before the explanation weight) and the gradient of the
+ * keys' time features.  keep (nullable = no dropout) is uint8 [rows*n_head*n_ngh], the byte of (row r, head h,
+ * neighbour j) at (r*n_head + h)*n_ngh + j -- the layout of the reference's dropped tensor
+ * [B*N_src*n_head, 1, N]; 1 = kept, a kept probability is scaled by keep_scale = 1 / (1 - p):
+ *     z[r,h] = sum_j softmax(s)_j * keep_j * keep_scale * ew[m,j] * key[r,j]
+ * stats holds the plain softmax's max and sum.  With keep == NULL, z and stats are tm_tgat_attn_fwd's bits.
+ * Limits: those of tm_tgat_attn_fwd, and tm_tgat_attn_bwd's bound on n_ngh (TM_E_UNSUPPORTED). */
+int tm_tgat_attn_train_fwd(const tm_tgat_attn *a, const uint8_t *keep, float keep_scale, float *z, float *stats,
+                           void *stream);
+/* backward: tm_tgat_attn_bwd with e'_j = ew_j * keep_j * keep_scale for ew_j (d_ew_parts, nullable, holds
+ * d ew: p_j c_j keep_j keep_scale); d_qf is required.  d_time [2][d_time] (required when d_time > 0; written,
+ * not accumulated) is the gradient of time_w (row 0) and time_b (row 1) through the keys:
+ *     d time_w[c] = sum_{r,j} -sin(u) dt[r,j] dk_j[c],   d time_b[c] = sum_{r,j} -sin(u) dk_j[c],
+ *     u = fl(fl(dt[r,j] time_w[c]) + time_b[c]),   dk_j = sum_h (p_j e'_j gz[r,h] + (ds_j / T) qf[r,h])
+ * on the time columns.  The sum over slots takes no atomics: per-workgroup partials in `workspace`
+ * (tm_tgat_attn_train_workspace_bytes(rows, d_time) bytes), then a fixed-order fp64 sum, so two launches give
+ * the same bits.  With keep == NULL, d_ew_parts, d_node and d_qf are tm_tgat_attn_bwd's bits. */
+int tm_tgat_attn_train_bwd(const tm_tgat_attn *a, const uint8_t *keep, float keep_scale, const float *stats,
+                           const float *gz, float *d_ew_parts, float *d_node, float *d_qf, float *d_time,
+                           void *workspace, void *stream);
+int64_t tm_tgat_attn_train_workspace_bytes(int64_t rows, int32_t d_time);
+
 /* The layer tail after the attention (AttnModel :383-385, MultiHeadAttention :133-135, MergeLayer :24-34)
  * for `rows` source rows, fused, on fp32 MFMA:
  *     u   = z G^T + fc_b + query                z [rows, n_head*d_key], G = fc W_v [d_key, n_head*d_key]

@@ -19,83 +19,10 @@
 // feature's rounding and in the backward, which also returns the gradient of qf: TGAT's second layer
 // queries with the first layer's output, which depends on the explanation weights.
 // The kernels are a separate set on purpose: the TGN kernels keep their code and bitwise results.
-#include "common.h"
+#include "tgat_common.h"
 
 namespace tmk {
 namespace tgat {
-
-constexpr int ATT_MAXH = 4;
-constexpr int ATT_WAVES = 4;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <int KPL>
-struct KeyLane {
-    int seg[KPL];     // 0 node feature, 1 edge feature, 2 time feature, 3 padding
-    int off[KPL];     // column inside the segment
-    float tw[KPL], tb[KPL];
-};
-
-template <int KPL>
-__device__ __forceinline__ KeyLane<KPL> key_lane(const tm_tgat_attn &a, int lane) {
-    KeyLane<KPL> L;
-    const int dn = a.d_node, de = a.d_edge, dk = a.d_node + a.d_edge + a.d_time;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        const int c = lane + 64 * i;
-        L.seg[i] = c < dn ? 0 : c < dn + de ? 1 : c < dk ? 2 : 3;
-        L.off[i] = L.seg[i] == 0 ? c : L.seg[i] == 1 ? c - dn : L.seg[i] == 2 ? c - dn - de : 0;
-        L.tw[i] = L.seg[i] == 2 ? a.time_w[L.off[i]] : 0.f;
-        L.tb[i] = L.seg[i] == 2 ? a.time_b[L.off[i]] : 0.f;
-    }
-    return L;
-}
-
-// key[slot] -> k[] (this lane's elements); out-of-range ids set the flag and read row 0
-template <int KPL>
-__device__ __forceinline__ void build_key(const tm_tgat_attn &a, const KeyLane<KPL> &L, int64_t slot, float k[KPL]) {
-    const float *nrow, *erow;
-    if (a.node_idx) {
-        int32_t id = a.node_idx[slot];
-        if ((uint32_t)id >= (uint32_t)a.node_rows) {
-            if (a.err_flag) *a.err_flag = TM_E_ARG;
-            id = 0;
-        }
-        nrow = a.node_tab + (int64_t)id * a.d_node;
-    } else {
-        nrow = a.node_tab + slot * a.d_node;
-    }
-    if (a.edge_idx) {
-        int32_t id = a.edge_idx[slot];
-        if ((uint32_t)id >= (uint32_t)a.edge_rows) {
-            if (a.err_flag) *a.err_flag = TM_E_ARG;
-            id = 0;
-        }
-        erow = a.edge_tab + (int64_t)id * a.d_edge;
-    } else {
-        erow = a.edge_tab + slot * a.d_edge;
-    }
-    const float t = a.dt[slot];
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) {
-        float v = 0.f;
-        if (L.seg[i] == 0) v = nrow[L.off[i]];
-        else if (L.seg[i] == 1) v = erow[L.off[i]];
-        else if (L.seg[i] == 2) v = cos_rd(__fadd_rn(__fmul_rn(t, L.tw[i]), L.tb[i]));   // two roundings, never an fma
-        k[i] = v;
-    }
-}
-
-__device__ __forceinline__ int64_t pair_row(const tm_tgat_attn &a, int64_t r, int h) {
-    if (!a.head_major_rows) return r;
-    const int64_t seg = a.seg_rows > 0 ? a.seg_rows : a.rows;
-    const int64_t base = r - r % seg;
-    return base + ((r - base) * a.n_head + h) % seg;
-}
 
 // one online-softmax step of head state (m, l, acc) with key k
 template <int KPL>

@@ -1,0 +1,94 @@
+// Device helpers shared by the TGAT attention kernels (tgat_attn.hip: the frozen base model; tgat_train.hip:
+// the training pair): the lane layout of a key, the on-the-fly key build with TGAT's two-rounding time
+// feature, the head-major pairing of mask / weight rows and the 64-lane butterfly sum.
+#pragma once
+#include "common.h"
+
+namespace tmk {
+namespace tgat {
+
+constexpr int ATT_MAXH = 4;
+constexpr int ATT_WAVES = 4;
+
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// TimeEncode's argument t w + b with the product and the sum rounded separately (TGAT.py:236-237: a multiply,
+// then an in-place add).  The contraction is switched off for this block: hipcc's default -ffp-contract=fast
+// turns a product-sum into one v_fma_f32, also when it is spelled __fadd_rn(__fmul_rn(t, w), b) (plain * and +
+// in this toolchain's headers), and at arguments of 1e5 .. 1e6 the single rounding moves the cosine by up to 3e-2.
+__device__ __forceinline__ float time_arg(float t, float w, float b) {
+#pragma clang fp contract(off)
+    const float p = t * w;
+    return p + b;
+}
+
+template <int KPL>
+struct KeyLane {
+    int seg[KPL];     // 0 node feature, 1 edge feature, 2 time feature, 3 padding
+    int off[KPL];     // column inside the segment
+    float tw[KPL], tb[KPL];
+};
+
+template <int KPL>
+__device__ __forceinline__ KeyLane<KPL> key_lane(const tm_tgat_attn &a, int lane) {
+    KeyLane<KPL> L;
+    const int dn = a.d_node, de = a.d_edge, dk = a.d_node + a.d_edge + a.d_time;
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) {
+        const int c = lane + 64 * i;
+        L.seg[i] = c < dn ? 0 : c < dn + de ? 1 : c < dk ? 2 : 3;
+        L.off[i] = L.seg[i] == 0 ? c : L.seg[i] == 1 ? c - dn : L.seg[i] == 2 ? c - dn - de : 0;
+        L.tw[i] = L.seg[i] == 2 ? a.time_w[L.off[i]] : 0.f;
+        L.tb[i] = L.seg[i] == 2 ? a.time_b[L.off[i]] : 0.f;
+    }
+    return L;
+}
+
+// key[slot] -> k[] (this lane's elements); out-of-range ids set the flag and read row 0
+template <int KPL>
+__device__ __forceinline__ void build_key(const tm_tgat_attn &a, const KeyLane<KPL> &L, int64_t slot, float k[KPL]) {
+    const float *nrow, *erow;
+    if (a.node_idx) {
+        int32_t id = a.node_idx[slot];
+        if ((uint32_t)id >= (uint32_t)a.node_rows) {
+            if (a.err_flag) *a.err_flag = TM_E_ARG;
+            id = 0;
+        }
+        nrow = a.node_tab + (int64_t)id * a.d_node;
+    } else {
+        nrow = a.node_tab + slot * a.d_node;
+    }
+    if (a.edge_idx) {
+        int32_t id = a.edge_idx[slot];
+        if ((uint32_t)id >= (uint32_t)a.edge_rows) {
+            if (a.err_flag) *a.err_flag = TM_E_ARG;
+            id = 0;
+        }
+        erow = a.edge_tab + (int64_t)id * a.d_edge;
+    } else {
+        erow = a.edge_tab + slot * a.d_edge;
+    }
+    const float t = a.dt[slot];
+#pragma unroll
+    for (int i = 0; i < KPL; ++i) {
+        float v = 0.f;
+        if (L.seg[i] == 0) v = nrow[L.off[i]];
+        else if (L.seg[i] == 1) v = erow[L.off[i]];
+        else if (L.seg[i] == 2) v = cos_rd(time_arg(t, L.tw[i], L.tb[i]));   // two roundings, never an fma
+        k[i] = v;
+    }
+}
+
+__device__ __forceinline__ int64_t pair_row(const tm_tgat_attn &a, int64_t r, int h) {
+    if (!a.head_major_rows) return r;
+    const int64_t seg = a.seg_rows > 0 ? a.seg_rows : a.rows;
+    const int64_t base = r - r % seg;
+    return base + ((r - base) * a.n_head + h) % seg;
+}
+
+}  // namespace tgat
+}  // namespace tmk

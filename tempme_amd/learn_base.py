@@ -1,15 +1,18 @@
-"""Stage one of the reference's workflow, ``learn_base.py``, for ``--base_type graphmixer``: train the base model
-that ``temp_exp_main.py`` explains and ``enhance_main.py`` enhances.
+"""Stage one of the reference's workflow, ``learn_base.py``, for ``--base_type graphmixer`` and ``--base_type tgat``:
+train the base model that ``temp_exp_main.py`` explains and ``enhance_main.py`` enhances.
 
     python -m tempme_amd.learn_base -d uslegis_sampled --data_dir processed --base_type graphmixer
+    python -m tempme_amd.learn_base -d uslegis_sampled --data_dir processed --base_type tgat --n_layer 2
 
 restates learn_base.py: the chronological 0.70 / 0.85 split with 10 % of the later nodes masked out of training
 (:90-152), the training loop (:201-253), the evaluation (:43-73), early stopping on the test AP and the saved
 best model.  The training step runs on the HIP path of ``GraphMixer.train_on_hip()`` (tm_gm_train_fwd /
 tm_gm_train_bwd, csrc/graphmixer_train.hip); subgraphs come from the device ``NeighborFinder.find_k_hop`` and
-negatives from the device ``RandEdgeSampler`` (keyed draws: a seed reproduces an epoch exactly).
+negatives from the device ``RandEdgeSampler`` (keyed draws: a seed reproduces an epoch exactly).  With
+``--base_type tgat`` the step runs on ``TGAT.train_on_hip()`` (tm_tgat_attn_train_fwd / tm_tgat_attn_train_bwd,
+csrc/tgat_train.hip) over 2-hop subgraphs; TGAT is built for ``--n_layer 2`` only.
 
-TGN (stateful memory) and TGAT (dropout inside attention) training are not part of this module.
+TGN (stateful memory) training is not part of this module.
 """
 import argparse
 import math
@@ -21,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .tgat import TGAT
 
 degree_dict = {"wikipedia": 20, "reddit": 20, "uci": 30, "mooc": 60, "enron": 30, "enron_sampled": 30, "canparl": 30,
                "uslegis": 30, "uslegis_sampled": 30}
@@ -94,15 +98,28 @@ def split_data(g_df, seed=2023, device=None, finders=True, sampler_seed=0):
     return s
 
 
+def _is_tgat(base_model):
+    return isinstance(base_model, TGAT)
+
+
+def _contrast(base_model, batch):
+    """learn_base.py:227-232: TGAT takes if_explain, GraphMixer explain_weights / edge_attr."""
+    a = (batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, batch.sg_src, batch.sg_tgt, batch.sg_bgd)
+    if _is_tgat(base_model):
+        return base_model.contrast(*a, if_explain=False)
+    return base_model.contrast(*a, explain_weights=None, edge_attr=None)
+
+
 def make_batch(base_model, sampler, src, dst, ts, e_idx=None, event_ids=None):
-    """One batch as learn_base.py:215-226 assembles it: the negative destinations and the three sides' hop-1
-    subgraphs (device tensors; GraphMixer reads hop 1 only)."""
+    """One batch as learn_base.py:215-226 assembles it: the negative destinations and the three sides'
+    subgraphs (device tensors; GraphMixer reads hop 1 only, TGAT samples its num_layers hops)."""
     size = len(src)
     ev = None if event_ids is None else np.asarray(event_ids, dtype=np.int64)
     _, fake = sampler.sample(size, event_ids=ev, as_tensor=True)
     fake_np = fake.cpu().numpy()
-    finder, N = base_model.neighbor_sampler, base_model.num_neighbors
-    sgs = [finder.find_k_hop(1, roots, ts, N, e_idx_l=None, event_ids=ev, side=side, as_tensor=True)
+    tgat = _is_tgat(base_model)
+    finder, N = (base_model.ngh_finder if tgat else base_model.neighbor_sampler), base_model.num_neighbors
+    sgs = [finder.find_k_hop(base_model.num_layers if tgat else 1, roots, ts, N, e_idx_l=None, event_ids=ev, side=side, as_tensor=True)
            for roots, side in ((src, L.SIDE_SRC), (dst, L.SIDE_TGT), (fake_np, L.SIDE_BGD))]
     # everything the step reads is on the device already: train_step then copies nothing from the host and waits for nothing
     dev = finder.device
@@ -116,8 +133,7 @@ def train_step(base_model, optimizer, batch):
     BCEWithLogits(neg, 0), backward, step.  Returns (loss, pos, neg) as device tensors; nothing here waits for
     the device."""
     optimizer.zero_grad()
-    pos, neg = base_model.contrast(batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, batch.sg_src, batch.sg_tgt,
-                                   batch.sg_bgd, explain_weights=None, edge_attr=None)
+    pos, neg = _contrast(base_model, batch)
     crit = torch.nn.functional.binary_cross_entropy_with_logits
     loss = crit(pos, torch.ones_like(pos)) + crit(neg, torch.zeros_like(neg))
     loss.backward()
@@ -180,8 +196,7 @@ def eval_one_epoch(args, base_model, sampler, src, dst, ts, label, val_e_idx_l=N
             e_l_cut = val_e_idx_l[s_idx:e_idx] if (val_e_idx_l is not None) else None
             batch = make_batch(base_model, sampler, src[s_idx:e_idx], dst[s_idx:e_idx], ts[s_idx:e_idx], e_l_cut,
                                event_ids=s_idx + np.arange(e_idx - s_idx))
-            pos, neg = base_model.contrast(batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, batch.sg_src,
-                                           batch.sg_tgt, batch.sg_bgd, explain_weights=None, edge_attr=None)
+            pos, neg = _contrast(base_model, batch)
             res.append(_metrics(pos, neg))
     acc, ap, auc = np.array(res).mean(axis=0)
     return acc, ap, None, auc
@@ -214,20 +229,28 @@ def main(argv=None):
 
     from .graphmixer import GraphMixer
     args = parser().parse_args(argv)
-    if args.base_type in ("tgn", "tgat"):
-        raise NotImplementedError(f"learn_base: --base_type {args.base_type} is not trained here; this module covers "
-                                  "the GraphMixer base only (TGN's stateful memory and TGAT's attention dropout "
-                                  "have no HIP training step yet)")
-    if args.base_type != "graphmixer":
+    if args.base_type == "tgn":
+        raise NotImplementedError("learn_base: --base_type tgn is not trained here; this module covers the GraphMixer "
+                                  "and TGAT bases (TGN's stateful memory has no HIP training step yet)")
+    if args.base_type not in ("graphmixer", "tgat"):
         raise ValueError(f"Wrong value for base_type {args.base_type}!")
+    if args.base_type == "tgat" and args.n_layer != 2:
+        # TGAT's own refusal (tgat.py), raised here before any file is read
+        raise NotImplementedError(f"learn_base: --base_type tgat needs --n_layer 2 (got --n_layer {args.n_layer}): "
+                                  f"num_layers {args.n_layer}: the explanation path samples 2-hop subgraphs, so only "
+                                  "num_layers=2 is built; only the GraphMixer base takes another depth")
     args.n_degree = degree_dict.get(args.data, args.n_degree)
     g_df = pd.read_csv(os.path.join(args.data_dir, f"ml_{args.data}.csv"))
     e_feat = np.load(os.path.join(args.data_dir, f"ml_{args.data}.npy"))
     n_feat = np.load(os.path.join(args.data_dir, f"ml_{args.data}_node.npy"))
     args.device = L.require_device(torch.device("cuda", args.gpu))
     sp = split_data(g_df, device=args.device, sampler_seed=args.seed)
-    base_model = GraphMixer(n_feat, e_feat, n_neighbors=args.n_degree, device=args.device, num_tokens=args.n_degree,
-                            num_layers=args.n_layer, dropout=args.drop_out).to(args.device)
+    if args.base_type == "tgat":
+        base_model = TGAT(n_feat, e_feat, num_layers=args.n_layer, num_neighbors=args.n_degree, n_head=args.n_head,
+                          drop_out=args.drop_out).to(args.device)
+    else:
+        base_model = GraphMixer(n_feat, e_feat, n_neighbors=args.n_degree, device=args.device,
+                                num_tokens=args.n_degree, num_layers=args.n_layer, dropout=args.drop_out).to(args.device)
     base_model.train_on_hip()
     optimizer = torch.optim.Adam(base_model.parameters(), lr=args.lr)
     num_instance = len(sp.train_src_l)

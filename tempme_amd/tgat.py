@@ -22,7 +22,15 @@ LayerNorm, the two-branch MergeLayer) runs as torch ops on the device (different
 ``model.fused_tail = True`` a contrast that needs no gradient runs it as one fused fp32-MFMA kernel
 (``tm_tgat_merge_fwd``) instead, which is built and tested but slower at the metric's shape, so off by default.  Gradients reach the explanation weights of all
 three passes: ``tm_tgat_attn_bwd`` returns d ew, the gradient of the dense neighbour table (h1') and the
-gradient of the folded query (through h0').  The base model is frozen: its parameters get no .grad.
+gradient of the folded query (through h0').  On these paths the base model is frozen: its parameters get no .grad.
+
+Training the base itself (learn_base.py) is opt-in: after ``model.train_on_hip()``, ``model.train()`` calls of
+``contrast(..., if_explain=False)`` / ``get_node_emb`` with gradients enabled run ``tm_tgat_attn_train_fwd`` /
+``tm_tgat_attn_train_bwd`` (csrc/tgat_train.hip): the attention dropout as a keep mask inside the kernels, fc's
+dropout in the torch tail, P = W_k^T W_q and G = fc W_v folded in fp32 from the live parameters under autograd (so
+d qf and d z reach w_qs, w_ks, w_vs and fc), the query-side time features as differentiable torch ops and the
+key-side time gradient from the kernel's d_time.  ``loss.backward()`` then fills .grad on all 36 trainable
+parameters.
 """
 import numpy as np
 import torch
@@ -160,6 +168,44 @@ class _TgatAttnFn(torch.autograd.Function):
                 d_ew = parts.view(R, H, N).sum(1)
             d_ew = d_ew.reshape(ew.shape)
         return d_qf, d_node, d_ew, None
+
+
+class _TgatTrainAttnFn(torch.autograd.Function):
+    """z = tm_tgat_attn_train_fwd(...) with the attention dropout's keep mask; backward through
+    tm_tgat_attn_train_bwd: the folded query, the dense neighbour table (pass 3's h1') and, through the keys'
+    time features, TimeEncode's basis_freq and phase."""
+
+    @staticmethod
+    def forward(ctx, qf, ngh_dense, freq, phase, spec, keep, keep_scale):
+        dev = qf.device
+        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
+        desc = _desc(spec, qf, ngh_dense, None)
+        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
+        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
+        L.check(L.lib().tm_tgat_attn_train_fwd(L.C.byref(desc), L.ptr(keep), keep_scale, L.ptr(z), L.ptr(stats),
+                                               L.stream_ptr(dev)), "TGAT training attention")
+        ctx.spec, ctx.keep, ctx.keep_scale = spec, keep, keep_scale
+        # the backward recomputes the keys from basis_freq and phase: saved, so that an in-place change of either
+        # between forward and backward is caught by autograd's version check
+        ctx.save_for_backward(qf, ngh_dense, stats, freq, phase)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        qf, ngh_dense, stats, freq, phase = ctx.saved_tensors
+        spec = dict(ctx.spec, time_w=freq, time_b=phase)
+        R, dT = spec["rows"], spec["d_time"]
+        dev = gz.device
+        gz = gz.contiguous().float()
+        d_node = torch.empty_like(ngh_dense) if ngh_dense is not None else None
+        d_qf = torch.empty_like(qf)
+        d_time = torch.empty((2, dT), dtype=torch.float32, device=dev)
+        ws = torch.empty(int(L.lib().tm_tgat_attn_train_workspace_bytes(R, dT)), dtype=torch.uint8, device=dev)
+        desc = _desc(spec, qf, ngh_dense, None)
+        L.check(L.lib().tm_tgat_attn_train_bwd(L.C.byref(desc), L.ptr(ctx.keep), ctx.keep_scale, L.ptr(stats),
+                                               L.ptr(gz), None, L.ptr(d_node), L.ptr(d_qf), L.ptr(d_time), L.ptr(ws),
+                                               L.stream_ptr(dev)), "TGAT training attention backward")
+        return d_qf, d_node, d_time[0], d_time[1], None, None, None
 
 
 def _desc(spec, qf, ngh_dense, ew):
@@ -327,7 +373,9 @@ class TGAT(nn.Module):
             return merge_fwd(z, query, lw, fd)
         return merge_torch(z, query, lw, fd)
 
-    def _check_mode(self):
+    def _check_mode(self, weights=None):
+        if weights is None and self._train_hip_ok():
+            return
         if self.training and self.dropout_p > 0:
             raise NotImplementedError("TGAT in training mode with drop_out > 0: the attention and fc dropout of "
                                       "the reference are not built (the frozen base model runs in eval mode)")
@@ -339,9 +387,10 @@ class TGAT(nn.Module):
         of a contrast, times the ratios of a threshold_test): every row gives the same result as in its own
         call, the head-major pairing stays inside its segment.  cut_time: one time per row, or per row of
         one segment (repeated)."""
-        self._check_mode()
-        pk = self._pack()
-        dev = pk["dev"]
+        train = explain_weights is None and self._train_hip_ok()
+        self._check_mode(explain_weights)
+        pk = None if train else self._pack()
+        dev = self._dev() if train else pk["dev"]
         i32, f64 = torch.int32, torch.float64
         n0 = _as_dev(nodes[0], dev, torch.long).reshape(-1)
         R = n0.shape[0]
@@ -362,6 +411,8 @@ class TGAT(nn.Module):
         t2 = _as_dev(times[1], dev, f64).reshape(R, N, N)
         dt1 = (cut.view(R, 1) - t1).float().contiguous()                   # retrieve_time_features :653-666
         dt2 = (t1.view(R, N, 1) - t2).float().contiguous()
+        if train:
+            return self._embed_train(dev, R, N, seg, n0, n1, n2, e1, e2, dt1, dt2)
         ew1 = ew2 = None
         if explain_weights is not None:
             ew1 = explain_weights[0].to(dev, torch.float32).reshape(R, N).contiguous()
@@ -373,16 +424,118 @@ class TGAT(nn.Module):
         h1 = self._attn_pass(pk, 0, tab[n1.reshape(-1).long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N)
         return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg)
 
+    # -------------------------------------------------------------- HIP training path (tm_tgat_attn_train_*)
+    def train_on_hip(self, flag=True):
+        """Opt in to (or out of) the HIP training step: with the flag set, ``model.train()`` calls of contrast /
+        get_node_emb with gradients enabled and ``if_explain`` false run tm_tgat_attn_train_fwd /
+        tm_tgat_attn_train_bwd with the reference's two dropouts, and ``loss.backward()`` fills ``.grad`` on all
+        36 trainable parameters (learn_base.py).  Default off: every other call keeps its path."""
+        self._train_on_hip = bool(flag)
+        self._train_checked = None
+        return self
+
+    def _apply(self, fn, *args, **kwargs):
+        self._train_checked = None          # .to() / .float() / ...: the parameters are looked at again
+        return super()._apply(fn, *args, **kwargs)
+
+    def _train_hip_ok(self):
+        return bool(getattr(self, "_train_on_hip", False)) and self.training and torch.is_grad_enabled()
+
+    def keep_mask_shapes(self, R, N):
+        """Shapes of one step's six keep masks for R stacked rows: the attention masks of the three passes
+        (flat, the byte of (row, head, neighbour) at (row H + head) N + neighbour: the reference's dropped tensor
+        [B*N_src*n_head, 1, N]) and the masks of fc's dropout on fc(out), [rows, model_dim]."""
+        H, dm = self.attn_model_list[0].multi_head_target.n_head, self.model_dim
+        return [(R * H * N,), (R * N * H * N,), (R * H * N,), (R, dm), (R * N, dm), (R, dm)]
+
+    def draw_keep_masks(self, R, N, generator=None):
+        """One step's keep masks (uint8, 1 = kept with probability 1 - drop_out) for R stacked rows, drawn on
+        the device in one allocation: [attn pass 1, attn pass 2, attn pass 3, fc pass 1, fc pass 2, fc pass 3]."""
+        shapes = self.keep_mask_shapes(R, N)
+        sizes = [int(np.prod(sh)) for sh in shapes]
+        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=self._dev()).bernoulli_(
+            1.0 - float(self.dropout_p), generator=generator)
+        return [x.view(sh) for x, sh in zip(flat.split(sizes), shapes)]
+
+    def _fold_live(self, am):
+        """Pt [dm, H dm] and Gt [H dm, dm] of pack_attn_model from the live parameters, in fp32 under autograd."""
+        mh = am.multi_head_target
+        H, dh = mh.n_head, mh.d_k
+        dm = mh.w_qs.weight.shape[1]
+        wq, wk, wv = (w.weight.view(H, dh, dm) for w in (mh.w_qs, mh.w_ks, mh.w_vs))
+        Pt = torch.einsum("hoi,hoq->qhi", wk, wq).reshape(dm, H * dm)
+        Gt = torch.einsum("qho,hoi->hiq", mh.fc.weight.view(dm, H, dh), wv).reshape(H * dm, dm)
+        return Pt, Gt
+
+    def _train_pass(self, am, folded, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, seg, akeep,
+                    fkeep, scale):
+        """_attn_pass on the live parameters with both dropouts -> [R, feat]."""
+        mh, mg = am.multi_head_target, am.merger
+        Pt, Gt = folded
+        fd, dm = self.feat_dim, self.model_dim
+        te = self.time_encoder
+        query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)
+        qf = (query @ Pt).contiguous()
+        spec = dict(rows=R, n_ngh=N, n_head=mh.n_head, d_key=dm, d_node=fd, d_edge=self.e_feat_dim,
+                    d_time=self.time_dim, node_rows=self.n_feat_th.shape[0], edge_rows=self.e_feat_th.shape[0],
+                    head_major=self.head_major_rows, temperature=mh.temperature, node_tab=self.n_feat_th,
+                    node_idx=node_idx, edge_tab=self.e_feat_th, edge_idx=edge_idx, dt=dt, time_w=te.basis_freq.detach(),
+                    time_b=te.phase.detach(), mask_node=mask_node, err=self._train_err, seg_rows=seg)
+        z = _TgatTrainAttnFn.apply(qf, ngh_dense, te.basis_freq, te.phase, spec, akeep, scale)
+        out = torch.addmm(mh.fc.bias, z, Gt)
+        if fkeep is not None:
+            out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (TGAT.py:134)
+        h = F.layer_norm(out + query, (dm,), mh.layer_norm.weight, mh.layer_norm.bias, 1e-5)
+        return mg(h, query[:, :fd])
+
+    def _embed_train(self, dev, R, N, seg, n0, n1, n2, e1, e2, dt1, dt2):
+        """The three passes of node_embeddings on the HIP training path (no explanation weights)."""
+        te = self.time_encoder
+        if getattr(self, "_train_checked", None) != dev:       # once per train_on_hip() / .to(), not per step
+            for p in self.parameters():
+                if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError("TGAT.train_on_hip: parameters must be contiguous fp32 on the HIP device")
+            self._train_checked = dev
+        if getattr(self, "_train_err", None) is None or self._train_err.device != dev:
+            self._train_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        p = float(self.dropout_p)
+        keep = getattr(self, "tgat_keep_masks", None)
+        if keep is None and p > 0.0:
+            keep = self.draw_keep_masks(R, N)
+        if keep is not None:
+            shapes = self.keep_mask_shapes(R, N)
+            if len(keep) != 6 or any(k.dtype != torch.uint8 or k.device != dev or k.numel() != int(np.prod(sh))
+                                     for k, sh in zip(keep, shapes)):
+                raise ValueError("TGAT.tgat_keep_masks: expected draw_keep_masks(R, N)'s six uint8 masks on the device")
+            keep = [k.contiguous().view(sh) for k, sh in zip(keep, shapes)]
+        else:
+            keep = [None] * 6
+        scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+        tab = self.n_feat_th
+        freq, phase = te.basis_freq, te.phase
+        t_root = torch.cos(torch.zeros_like(freq) * freq + phase).expand(R, -1)          # TimeEncode(0)
+        t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)                           # two roundings (mul, then add)
+        am0, am1 = self.attn_model_list
+        f0, f1 = self._fold_live(am0), self._fold_live(am1)
+        h0 = self._train_pass(am0, f0, tab[n0], t_root, R, N, n1, None, e1, dt1, n1, seg, keep[0], keep[3], scale)
+        h1 = self._train_pass(am0, f0, tab[n1.reshape(-1).long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, seg * N,
+                              keep[1], keep[4], scale)
+        out = self._train_pass(am1, f1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, seg, keep[2], keep[5],
+                               scale)
+        self._tgat_train_key = (R, N, keep[0] is not None)   # marker: the HIP training path ran
+        return out
+
     def check_errors(self):
         """Raise if a kernel saw an out-of-range node or edge index (synchronises)."""
         pk = self._pack_cache
-        if pk is not None and int(pk["err"].item()) != 0:
-            pk["err"].zero_()
-            raise IndexError("TGAT: node or edge index out of range of the feature tables")
+        for err in ((pk or {}).get("err"), getattr(self, "_train_err", None)):
+            if err is not None and int(err.item()) != 0:
+                err.zero_()
+                raise IndexError("TGAT: node or edge index out of range of the feature tables")
 
     def _sides(self, roots, subgraphs, weights, cut_time):
         """Stack the sides of a contrast into one node_embeddings call -> list of [B, feat]."""
-        self._check_mode()
+        self._check_mode(weights)
         dev = self._dev()
         S = len(roots)
         n0 = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in roots])
@@ -425,7 +578,10 @@ class TGAT(nn.Module):
                                           [subgraph_src, subgraph_tgt, subgraph_src, subgraph_bgd],
                                           [w_s, w_t, w_s2, w_b], cut_time_l)
         B = s.shape[0]
-        score = self.affinity(torch.cat([s, s2], dim=0), torch.cat([t, b], dim=0))
+        if not if_explain and self._train_hip_ok():
+            score = self.affinity_score(torch.cat([s, s2], dim=0), torch.cat([t, b], dim=0))   # the live parameters
+        else:
+            score = self.affinity(torch.cat([s, s2], dim=0), torch.cat([t, b], dim=0))
         return score[:B], score[B:]
 
     def get_node_emb(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, e_idx_l, subgraph_src, subgraph_tgt,

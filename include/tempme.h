@@ -624,6 +624,47 @@ int tm_tgn_attn_fwd(const tm_tgn_attn *a, float *z, float *stats, void *stream);
 int tm_tgn_attn_bwd(const tm_tgn_attn *a, const float *stats, const float *gz, float *d_ew_parts, float *d_node,
                     void *stream);
 
+/* Training pair of the same layer (learn_base.py for --base_type tgn): the attention dropout of
+ * ScaledDotProductAttention (after the softmax, before the explanation weight) and the gradients a trainable
+ * base model needs.  keep (nullable = no dropout) is uint8 [rows*n_head*n_ngh], the byte of (row r, head h,
+ * neighbour j) at (r*n_head + h)*n_ngh + j -- the layout of the reference's dropped tensor:
+ *     z[r,h] = sum_j softmax(s)_j * keep_j * keep_scale * ew[m,j] * key[r,j]
+ * stats holds the plain softmax's max and sum.  With keep == NULL, z and stats are tm_tgn_attn_fwd's bits.
+ * Limits: those of tm_tgn_attn_fwd, and tm_tgn_attn_bwd's bound on n_ngh (TM_E_UNSUPPORTED). */
+int tm_tgn_attn_train_fwd(const tm_tgn_attn *a, const uint8_t *keep, float keep_scale, float *z, float *stats,
+                          void *stream);
+/* backward: tm_tgn_attn_bwd with e'_j = ew_j * keep_j * keep_scale for ew_j (d_ew_parts, nullable, holds
+ * d ew: p_j c_j keep_j keep_scale); d_qf [rows, n_head*d_key] is required; d_node (nullable) as there, for a
+ * dense node table.  d_time [2][d_time] (required when d_time > 0; written, not accumulated) is the gradient
+ * of time_w (row 0) and time_b (row 1) through the keys:
+ *     d time_w[c] = sum_{r,j} -sin(u) dt[r,j] dk_j[c],   d time_b[c] = sum_{r,j} -sin(u) dk_j[c],
+ * u = fma(dt, time_w, time_b), the argument the key's cosine took.  No atomics: one partial per workgroup in
+ * `workspace` (tm_tgn_attn_train_workspace_bytes(rows, d_time) bytes), then a fixed-order fp64 sum, so two
+ * launches give the same bits.  slot_ab (nullable) [rows, n_ngh, n_head, 2] receives, per slot and head,
+ * a = p_j e'_j and b = ds_j / temperature: dk_j = sum_h a gz[r,h] + b qf[r,h], which tm_tgn_attn_train_dtab
+ * reduces into the rows of a gathered node table.  With keep == NULL, d_ew_parts and d_node are
+ * tm_tgn_attn_bwd's bits. */
+int tm_tgn_attn_train_bwd(const tm_tgn_attn *a, const uint8_t *keep, float keep_scale, const float *stats,
+                          const float *gz, float *d_ew_parts, float *d_node, float *d_qf, float *d_time,
+                          float *slot_ab, void *workspace, void *stream);
+int64_t tm_tgn_attn_train_workspace_bytes(int64_t rows, int32_t d_time);
+/* Gradient of a GATHERED node table (a->node_idx != NULL): d_tab [node_rows, d_node], written (rows without a
+ * slot are zero), from the backward's slot_ab and the same a->qf and gz.  The [rows*n_ngh, d_node] tensor of
+ * per-slot gradients is never formed.  order [n_order] lists slots (r*n_ngh + j, int64) grouped by table row:
+ * the entries seg_off[v] .. seg_off[v+1]-1 are the slots whose node_idx is v (seg_off [node_rows+1], int64) --
+ * a stable sort of node_idx and its segment offsets.  One workgroup per table row adds its list in a fixed
+ * order: no atomics, the same bits on every launch.  Rows below row_begin are stored as zero and their lists
+ * are not read (row 0 is the padding node: it gathers a large share of the slots and feeds nothing trainable).
+ * An entry of order outside [0, rows*n_ngh) sets a->err_flag and is skipped. */
+int tm_tgn_attn_train_dtab(const tm_tgn_attn *a, const float *slot_ab, const float *gz, const int64_t *order,
+                           int64_t n_order, const int64_t *seg_off, int32_t row_begin, float *d_tab, void *stream);
+/* The dense form of the same reduction, the backward of out = tab[idx]: out [out_rows, d] with
+ * out[v] = sum of grad[order[i]] over i in [seg_off[v], seg_off[v+1]) (grad [n_rows, d], d <= 512), in the
+ * list's order, without atomics (torch's index_select backward adds with atomics). */
+int tm_tgn_rows_reduce(const float *grad, int64_t n_rows, int32_t d, const int64_t *order, int64_t n_order,
+                       const int64_t *seg_off, int32_t out_rows, int32_t row_begin, float *out, int32_t *err_flag,
+                       void *stream);
+
 /* ---------------------------------------------------------------- TGAT base model (consumer of the path)
  * One attention pass of the base TGAT (TGAT/TGAT.py: forward_msg_layer :678-706 -> AttnModel :362-386 ->
  * MultiHeadAttention :110-137 -> ScaledDotProductAttention :64-80), the part that touches every

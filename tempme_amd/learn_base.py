@@ -1,8 +1,9 @@
-"""Stage one of the reference's workflow, ``learn_base.py``, for ``--base_type graphmixer`` and ``--base_type tgat``:
+"""Stage one of the reference's workflow, ``learn_base.py``, for its three base models:
 train the base model that ``temp_exp_main.py`` explains and ``enhance_main.py`` enhances.
 
     python -m tempme_amd.learn_base -d uslegis_sampled --data_dir processed --base_type graphmixer
     python -m tempme_amd.learn_base -d uslegis_sampled --data_dir processed --base_type tgat --n_layer 2
+    python -m tempme_amd.learn_base -d uslegis_sampled --data_dir processed --base_type tgn --n_layer 2
 
 restates learn_base.py: the chronological 0.70 / 0.85 split with 10 % of the later nodes masked out of training
 (:90-152), the training loop (:201-253), the evaluation (:43-73), early stopping on the test AP and the saved
@@ -12,7 +13,14 @@ negatives from the device ``RandEdgeSampler`` (keyed draws: a seed reproduces an
 ``--base_type tgat`` the step runs on ``TGAT.train_on_hip()`` (tm_tgat_attn_train_fwd / tm_tgat_attn_train_bwd,
 csrc/tgat_train.hip) over 2-hop subgraphs; TGAT is built for ``--n_layer 2`` only.
 
-TGN (stateful memory) training is not part of this module.
+With ``--base_type tgn`` the step runs on ``TGN.train_on_hip()`` (tm_tgn_attn_train_fwd / tm_tgn_attn_train_bwd /
+tm_tgn_attn_train_dtab, csrc/tgn_train.hip) with the stateful memory on the device: every step applies the pending
+messages, persists the positives' memory and stores the batch's raw messages (TGN/tgn.py:123-196), and
+``memory.detach_memory()`` follows ``optimizer.step()``.  As in the reference the memory is never re-initialised
+between epochs, and each epoch's evaluation (which moves the memory on, batch by batch) runs between
+``backup_memory()`` and ``restore_memory()``.  TGN reads 2-hop subgraphs, so ``--n_layer 2`` is required.  Next to
+the best model's ``state_dict`` (``<prefix>tgn_<data>.pt``) the pending messages of the training memory are saved
+as ``<prefix>tgn_<data>_messages.pt`` ({"nodes", "raw", "ts"} tensors; ``TGN.load_pending_messages`` reads them).
 """
 import argparse
 import math
@@ -25,6 +33,7 @@ import torch
 
 from . import _lib as L
 from .tgat import TGAT
+from .tgn import TGN
 
 degree_dict = {"wikipedia": 20, "reddit": 20, "uci": 30, "mooc": 60, "enron": 30, "enron_sampled": 30, "canparl": 30,
                "uslegis": 30, "uslegis_sampled": 30}
@@ -102,8 +111,12 @@ def _is_tgat(base_model):
     return isinstance(base_model, TGAT)
 
 
+def _is_tgn(base_model):
+    return isinstance(base_model, TGN)
+
+
 def _contrast(base_model, batch):
-    """learn_base.py:227-232: TGAT takes if_explain, GraphMixer explain_weights / edge_attr."""
+    """learn_base.py:227-232: TGAT takes if_explain, GraphMixer and TGN explain_weights / edge_attr."""
     a = (batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, batch.sg_src, batch.sg_tgt, batch.sg_bgd)
     if _is_tgat(base_model):
         return base_model.contrast(*a, if_explain=False)
@@ -112,14 +125,18 @@ def _contrast(base_model, batch):
 
 def make_batch(base_model, sampler, src, dst, ts, e_idx=None, event_ids=None):
     """One batch as learn_base.py:215-226 assembles it: the negative destinations and the three sides'
-    subgraphs (device tensors; GraphMixer reads hop 1 only, TGAT samples its num_layers hops)."""
+    subgraphs (device tensors; GraphMixer reads hop 1 only, TGAT samples its num_layers hops, TGN 2 hops)."""
     size = len(src)
     ev = None if event_ids is None else np.asarray(event_ids, dtype=np.int64)
     _, fake = sampler.sample(size, event_ids=ev, as_tensor=True)
     fake_np = fake.cpu().numpy()
-    tgat = _is_tgat(base_model)
-    finder, N = (base_model.ngh_finder if tgat else base_model.neighbor_sampler), base_model.num_neighbors
-    sgs = [finder.find_k_hop(base_model.num_layers if tgat else 1, roots, ts, N, e_idx_l=None, event_ids=ev, side=side, as_tensor=True)
+    tgat, tgn = _is_tgat(base_model), _is_tgn(base_model)
+    if tgn:
+        finder = base_model.embedding_module.neighbor_sampler
+    else:
+        finder = base_model.ngh_finder if tgat else base_model.neighbor_sampler
+    N = base_model.num_neighbors
+    sgs = [finder.find_k_hop(2 if tgn else base_model.num_layers if tgat else 1, roots, ts, N, e_idx_l=None, event_ids=ev, side=side, as_tensor=True)
            for roots, side in ((src, L.SIDE_SRC), (dst, L.SIDE_TGT), (fake_np, L.SIDE_BGD))]
     # everything the step reads is on the device already: train_step then copies nothing from the host and waits for nothing
     dev = finder.device
@@ -138,6 +155,8 @@ def train_step(base_model, optimizer, batch):
     loss = crit(pos, torch.ones_like(pos)) + crit(neg, torch.zeros_like(neg))
     loss.backward()
     optimizer.step()
+    if _is_tgn(base_model):
+        base_model.memory.detach_memory()       # learn_base.py:238-239
     return loss.detach(), pos.detach(), neg.detach()
 
 
@@ -229,10 +248,12 @@ def main(argv=None):
 
     from .graphmixer import GraphMixer
     args = parser().parse_args(argv)
-    if args.base_type == "tgn":
-        raise NotImplementedError("learn_base: --base_type tgn is not trained here; this module covers the GraphMixer "
-                                  "and TGAT bases (TGN's stateful memory has no HIP training step yet)")
-    if args.base_type not in ("graphmixer", "tgat"):
+    if args.base_type == "tgn" and args.n_layer != 2:
+        raise NotImplementedError(f"learn_base: --base_type tgn needs --n_layer 2 (got --n_layer {args.n_layer}): TGN "
+                                  "reads 2-hop subgraphs and only two attention layers ever run, so a third would "
+                                  "hold parameters the step never trains; only the GraphMixer base takes another "
+                                  "depth")
+    if args.base_type not in ("graphmixer", "tgat", "tgn"):
         raise ValueError(f"Wrong value for base_type {args.base_type}!")
     if args.base_type == "tgat" and args.n_layer != 2:
         # TGAT's own refusal (tgat.py), raised here before any file is read
@@ -248,6 +269,9 @@ def main(argv=None):
     if args.base_type == "tgat":
         base_model = TGAT(n_feat, e_feat, num_layers=args.n_layer, num_neighbors=args.n_degree, n_head=args.n_head,
                           drop_out=args.drop_out).to(args.device)
+    elif args.base_type == "tgn":
+        base_model = TGN(n_feat, e_feat, n_neighbors=args.n_degree, device=args.device, n_layers=args.n_layer,
+                         n_heads=args.n_head, dropout=args.drop_out).to(args.device)
     else:
         base_model = GraphMixer(n_feat, e_feat, n_neighbors=args.n_degree, device=args.device,
                                 num_tokens=args.n_degree, num_layers=args.n_layer, dropout=args.drop_out).to(args.device)
@@ -269,13 +293,22 @@ def main(argv=None):
         print("train acc: {}, train ap: {}, train auc:{}, loss: {}".format(tr.get("acc"), tr.get("ap"), tr.get("auc"),
                                                                           np.mean(tr["loss"])))
         base_model.set_neighbor_sampler(sp.full_ngh_finder)
+        tgn = args.base_type == "tgn"
+        if tgn:
+            memory_backup = base_model.memory.backup_memory()      # the evaluation moves the memory on
         test_acc, test_ap, _, test_auc = eval_one_epoch(args, base_model, sp.test_rand_sampler, sp.test_src_l,
                                                         sp.test_dst_l, sp.test_ts_l, sp.test_label_l, sp.test_e_idx_l)
+        if tgn:
+            base_model.memory.restore_memory(memory_backup)        # never re-initialised: training goes on from here
         print("test acc: {}, test ap: {}, test auc: {}".format(test_acc, test_ap, test_auc))
         if test_ap > best_aps:
             os.makedirs(args.out_dir, exist_ok=True)
             path = os.path.join(args.out_dir, f"{args.prefix}{args.base_type}_{args.data}.pt")
             torch.save(base_model.state_dict(), path)
+            if tgn:
+                # the training memory is restored: its pending messages go next to the state_dict
+                torch.save({k: v.cpu() for k, v in base_model.pending_messages().items()},
+                           os.path.join(args.out_dir, f"{args.prefix}tgn_{args.data}_messages.pt"))
             print(f"save model to {path}")
             best_aps = test_ap
         if early_stopper.early_stop_check(test_ap):

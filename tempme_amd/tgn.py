@@ -18,9 +18,21 @@ constructor, submodule names (a reference ``state_dict`` loads as is), construct
     temp_exp_main.py:624-631) come from ``tgn_attn_bwd_kernel`` (``tm_tgn_attn_bwd``) and torch
     autograd for the dense per-row algebra.  The base model is frozen: its parameters get no .grad.
 
-Scope: the ``forbidden_memory_update=True`` path TempME uses (temp_exp_main.py:703-704), the
-"graph_attention" embedding module, 2-hop subgraphs.  Memory messages stored on the model are
-applied through get_updated_memory semantics (tgn.py:237-248) once per memory state.
+Scope: the "graph_attention" embedding module, 2-hop subgraphs.  With ``forbidden_memory_update=True`` (the path
+TempME uses, temp_exp_main.py:703-704) the model is frozen: memory messages stored on the model are applied through
+get_updated_memory semantics (tgn.py:237-248) once per memory state.
+
+With ``forbidden_memory_update=False`` (the constructor's default, as learn_base.py trains the base model) contrast
+and get_node_emb are stateful as tgn.py:123-196: they embed over the updated memory, persist the positives' memory,
+clear their messages and store the batch's raw messages.  The state lives on the device (``Memory.msg_raw`` /
+``msg_ts`` / ``msg_flag``: under the ``last`` aggregator one raw message per node is all the reference reads) and
+moves on without a loop over events and without a host synchronisation.  After ``train_on_hip()`` a ``train()``
+step runs the training pair ``tm_tgn_attn_train_fwd`` / ``tm_tgn_attn_train_bwd`` (csrc/tgn_train.hip) with the
+reference's two dropouts on the live parameters, and ``loss.backward()`` fills ``.grad`` on every tensor the
+reference's step trains -- TimeEncode, the message MLP and the GRU cell (through the updated memory rows the keys
+and queries gather: ``tm_tgn_attn_train_dtab`` / ``tm_tgn_rows_reduce``, no atomics), the two attention layers and
+``affinity_score``.  ``messages_to_dict()`` / ``messages_from_dict()`` move the pending messages between the device
+store and ``memory.messages``, which the frozen path reads (it calls the former itself when the store is newer).
 """
 from collections import defaultdict
 
@@ -116,6 +128,13 @@ class Memory(nn.Module):
         self.memory = nn.Parameter(torch.zeros((self.n_nodes, self.memory_dimension)), requires_grad=False)
         self.last_update = nn.Parameter(torch.zeros(self.n_nodes), requires_grad=False)
         self.messages = defaultdict(list)
+        # the pending store of the stateful path (TGN.contrast with forbidden_memory_update=False): under the
+        # ``last`` aggregator only a node's last raw message is ever read, so one row, its timestamp and a flag
+        # per node hold what the reference's dict of lists holds.  ``store_is_newer``: the store has moved on
+        # from ``messages`` (TGN.messages_to_dict() writes it back); else ``messages`` is what counts
+        self.msg_raw = self.msg_ts = self.msg_flag = None
+        self.store_is_newer = False
+        self.store_any = False          # host-side: some node may have a pending message in the store
 
     def store_raw_messages(self, nodes, node_id_to_messages):
         for node in nodes:
@@ -124,12 +143,54 @@ class Memory(nn.Module):
     def get_memory(self, node_idxs):
         return self.memory[node_idxs, :]
 
+    def set_memory(self, node_idxs, values):
+        """memory.py:42-43."""
+        with torch.no_grad():
+            self.memory[node_idxs, :] = values
+
     def get_last_update(self, node_idxs):
         return self.last_update[node_idxs]
 
     def clear_messages(self, nodes):
         for node in nodes:
             self.messages[node] = []
+
+    def ensure_store(self, raw_dimension, device):
+        """The device store [n_nodes, raw_dimension] (allocated empty on first use)."""
+        if self.msg_raw is None or self.msg_raw.device != device or self.msg_raw.shape[1] != raw_dimension:
+            self.msg_raw = torch.zeros((self.n_nodes, raw_dimension), dtype=torch.float32, device=device)
+            self.msg_ts = torch.zeros(self.n_nodes, dtype=torch.float32, device=device)
+            self.msg_flag = torch.zeros(self.n_nodes, dtype=torch.bool, device=device)
+            self.store_is_newer = self.store_any = False
+
+    def backup_memory(self):
+        """memory.py:48-53 -> (memory, last_update, messages) clones; a fourth entry holds the device store."""
+        messages_clone = {k: [(x[0].clone(), x[1].clone()) for x in v] for k, v in self.messages.items()}
+        store = None
+        if self.msg_raw is not None:
+            store = (self.msg_raw.clone(), self.msg_ts.clone(), self.msg_flag.clone(), self.store_is_newer,
+                     self.store_any)
+        return self.memory.data.clone(), self.last_update.data.clone(), messages_clone, store
+
+    def restore_memory(self, memory_backup):
+        """memory.py:55-60 (a three-entry backup, as the reference's, restores without a device store)."""
+        self.memory.data, self.last_update.data = memory_backup[0].clone(), memory_backup[1].clone()
+        self.messages = defaultdict(list)
+        for k, v in memory_backup[2].items():
+            self.messages[k] = [(x[0].clone(), x[1].clone()) for x in v]
+        store = memory_backup[3] if len(memory_backup) > 3 else None
+        if store is None:
+            self.msg_raw = self.msg_ts = self.msg_flag = None
+            self.store_is_newer = self.store_any = False
+        else:
+            self.msg_raw, self.msg_ts, self.msg_flag = store[0].clone(), store[1].clone(), store[2].clone()
+            self.store_is_newer, self.store_any = store[3], store[4]
+
+    def detach_memory(self):
+        """memory.py:62-71.  The device store never holds autograd history (it is written detached)."""
+        self.memory.detach_()
+        for k, v in self.messages.items():
+            self.messages[k] = [(m[0].detach(), m[1]) for m in v]
 
 
 class MLPMessageFunction(nn.Module):
@@ -244,6 +305,90 @@ class _TgnAttnFn(torch.autograd.Function):
         return None, d_node, d_ew, None
 
 
+def _rows_by_table_row(idx, n_rows):
+    """The entries of ``idx`` grouped by the table row they name, for the reductions without atomics: a stable
+    sort's permutation [len(idx)] and the segment offsets [n_rows + 1] (both int64, on idx's device; no host
+    synchronisation)."""
+    vals, order = torch.sort(idx.long(), stable=True)
+    seg = torch.searchsorted(vals, torch.arange(n_rows + 1, dtype=torch.long, device=idx.device))
+    return order.contiguous(), seg.contiguous()
+
+
+class _GatherRowsFn(torch.autograd.Function):
+    """tab[idx] whose backward adds the gradient rows of a table row in a fixed order (tm_tgn_rows_reduce)
+    where torch's index_select backward adds with atomics.  Table row 0 is the padding node: it feeds nothing
+    trainable and takes no gradient here."""
+
+    @staticmethod
+    def forward(ctx, tab, idx, err):
+        ctx.save_for_backward(idx)
+        ctx.err, ctx.tab_rows = err, tab.shape[0]
+        return tab.index_select(0, idx)
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, = ctx.saved_tensors
+        g = g.contiguous().float()
+        n, d = g.shape
+        out = torch.empty((ctx.tab_rows, d), dtype=torch.float32, device=g.device)
+        order, seg = _rows_by_table_row(idx, ctx.tab_rows)
+        L.check(L.lib().tm_tgn_rows_reduce(L.ptr(g), n, d, L.ptr(order), n, L.ptr(seg), ctx.tab_rows, 1, L.ptr(out),
+                                           L.ptr(ctx.err), L.stream_ptr(g.device)), "TGN row-gather backward")
+        return out, None, None
+
+
+class _TgnTrainAttnFn(torch.autograd.Function):
+    """z = tm_tgn_attn_train_fwd(...) with the attention dropout's keep mask; backward through
+    tm_tgn_attn_train_bwd: the folded query, TimeEncode's weight and bias through the keys' time features, and
+    the keys' node features -- the dense neighbour rows of layer 1, or the rows of the gathered table of layer 0
+    (tm_tgn_attn_train_dtab; no [rows*n_ngh, d_node] tensor is formed)."""
+
+    @staticmethod
+    def forward(ctx, qf, ngh_dense, tab, tw, tb, spec, keep, keep_scale):
+        dev = qf.device
+        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
+        spec = dict(spec, node_tab=tab, time_w=tw, time_b=tb)
+        desc = _desc(spec, qf, ngh_dense, None)
+        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
+        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
+        L.check(L.lib().tm_tgn_attn_train_fwd(L.C.byref(desc), L.ptr(keep), keep_scale, L.ptr(z), L.ptr(stats),
+                                              L.stream_ptr(dev)), "TGN training attention")
+        ctx.spec, ctx.keep, ctx.keep_scale = spec, keep, keep_scale
+        ctx.dense = ngh_dense is not None
+        # the backward rebuilds the keys: saved, so that an in-place change between forward and backward is
+        # caught by autograd's version check
+        ctx.save_for_backward(qf, ngh_dense if ctx.dense else tab, stats, tw, tb)
+        return z
+
+    @staticmethod
+    def backward(ctx, gz):
+        qf, node, stats, tw, tb = ctx.saved_tensors
+        spec = dict(ctx.spec, node_tab=node, time_w=tw, time_b=tb)
+        R, N, H, dT = spec["rows"], spec["n_ngh"], spec["n_head"], spec["d_time"]
+        dev = gz.device
+        lib = L.lib()
+        gz = gz.contiguous().float()
+        want_tab = not ctx.dense and ctx.needs_input_grad[2]
+        d_node = torch.empty_like(node) if ctx.dense and ctx.needs_input_grad[1] else None
+        d_qf = torch.empty_like(qf)
+        d_time = torch.empty((2, dT), dtype=torch.float32, device=dev)
+        ab = torch.empty((R, N, H, 2), dtype=torch.float32, device=dev) if want_tab else None
+        ws = torch.empty(int(lib.tm_tgn_attn_train_workspace_bytes(R, dT)), dtype=torch.uint8, device=dev)
+        desc = _desc(spec, qf, node if ctx.dense else None, None)
+        L.check(lib.tm_tgn_attn_train_bwd(L.C.byref(desc), L.ptr(ctx.keep), ctx.keep_scale, L.ptr(stats), L.ptr(gz),
+                                          None, L.ptr(d_node), L.ptr(d_qf), L.ptr(d_time), L.ptr(ab), L.ptr(ws),
+                                          L.stream_ptr(dev)), "TGN training attention backward")
+        d_tab = None
+        if want_tab:
+            order, seg = _rows_by_table_row(spec["node_idx"], node.shape[0])
+            d_tab = torch.empty_like(node)
+            # row 0 is the padding node: a large share of the slots, and nothing trainable behind it
+            L.check(lib.tm_tgn_attn_train_dtab(L.C.byref(desc), L.ptr(ab), L.ptr(gz), L.ptr(order), order.shape[0],
+                                               L.ptr(seg), 1, L.ptr(d_tab), L.stream_ptr(dev)),
+                    "TGN gathered-table gradient")
+        return d_qf, d_node, d_tab, d_time[0], d_time[1], None, None, None
+
+
 def _desc(spec, qf, ngh_dense, ew):
     a = L.TgnAttn()
     a.rows, a.n_ngh, a.n_head = spec["rows"], spec["n_ngh"], spec["n_head"]
@@ -335,6 +480,8 @@ class TGN(nn.Module):
         self.mean_time_shift_src, self.std_time_shift_src = mean_time_shift_src, std_time_shift_src
         self.mean_time_shift_dst, self.std_time_shift_dst = mean_time_shift_dst, std_time_shift_dst
         self.aggregator_type = aggregator_type
+        self.message_function_type = message_function
+        self.memory_updater_type = memory_updater_type
         if self.use_memory:
             self.memory_dimension = self.n_node_features
             self.memory_update_at_start = memory_update_at_start
@@ -373,6 +520,8 @@ class TGN(nn.Module):
         return L.require_device(p.device if p.device.type == "cuda" else None)
 
     def _param_key(self):
+        if self.use_memory and self.memory.store_is_newer:
+            self.messages_to_dict()      # the stateful path moved on: the frozen path reads memory.messages
         key = [(t.data_ptr(), t._version) for t in self.parameters()]
         if self.use_memory:
             key.append(tuple((n, len(v), id(v[-1][0]) if v else 0) for n, v in sorted(self.memory.messages.items())))
@@ -454,6 +603,284 @@ class TGN(nn.Module):
         self._pack_cache, self._pack_key = pack, key
         return pack
 
+    # -------------------------------------------------------------- the stateful path (tgn.py:100-199)
+    def train_on_hip(self, flag=True):
+        """Opt in to (or out of) the HIP training step: with the flag set and ``forbidden_memory_update`` False,
+        ``model.train()`` calls of contrast / get_node_emb / node_embeddings with gradients enabled run
+        tm_tgn_attn_train_fwd / tm_tgn_attn_train_bwd with the reference's two dropouts, ``loss.backward()``
+        fills ``.grad`` on every parameter the reference's step trains, and contrast / get_node_emb advance the
+        memory as tgn.py:167-191 does.  In ``eval()`` or under ``no_grad`` the stateful path needs no flag: it runs
+        without dropout and advances the memory the same way."""
+        self._train_on_hip = bool(flag)
+        self._live_checked = None
+        return self
+
+    def _apply(self, fn, *args, **kwargs):
+        self._live_checked = None          # .to() / .float() / ...: the parameters are looked at again
+        return super()._apply(fn, *args, **kwargs)
+
+    def _stateful(self):
+        """True when contrast / get_node_emb / node_embeddings update the memory (tgn.py:167); refuses the options
+        the stateful path does not restate, naming the option."""
+        if not self.use_memory or self.forbidden_memory_update:
+            return False
+        for name, got, want in (("memory_update_at_start", self.memory_update_at_start, True),
+                                ("aggregator_type", self.aggregator_type, "last"),
+                                ("message_function", self.message_function_type, "mlp"),
+                                ("memory_updater_type", self.memory_updater_type, "gru"),
+                                ("use_source_embedding_in_message", self.use_source_embedding_in_message, True),
+                                ("use_destination_embedding_in_message", self.use_destination_embedding_in_message,
+                                 True)):
+            if got != want:
+                raise NotImplementedError(f"TGN with memory updates (forbidden_memory_update=False): {name}={got!r} "
+                                          f"is not built; learn_base.py trains with {name}={want!r}")
+        if len(self.embedding_module.attention_models) < 2:
+            raise NotImplementedError("TGN with memory updates: n_layers < 2 (subgraphs are 2-hop: two attention "
+                                      "layers run)")
+        return True
+
+    def _live_dev(self):
+        """The device of the stateful path, its parameters checked once."""
+        dev = self._dev()
+        if getattr(self, "_live_checked", None) != dev:       # once per train_on_hip() / .to(), not per step
+            for p in self.parameters():
+                if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError("TGN with memory updates: parameters must be contiguous fp32 on the HIP "
+                                       "device (model.to(device))")
+            self._live_checked = dev
+        if getattr(self, "_live_err", None) is None or self._live_err.device != dev:
+            self._live_err = torch.zeros(1, dtype=torch.int32, device=dev)
+        return dev
+
+    def _raw_dim(self):
+        return 2 * self.memory_dimension + self.n_edge_features + self.time_encoder.dimension
+
+    def keep_mask_shapes(self, R1, N):
+        """Shapes of one step's four keep masks for R1 stacked root rows: the attention masks of layer 0 (hop-1
+        rows) and layer 1 (roots), flat with the byte of (row, head, neighbour) at (row H + head) N + neighbour
+        (the reference's dropped tensor [rows*n_head, 1, N]), then the masks of fc's dropout, [rows, d_query]."""
+        mh = self.embedding_module.attention_models[0].multi_head_target
+        H, dq = mh.n_head, 2 * self.n_node_features
+        return [(R1 * N * H * N,), (R1 * H * N,), (R1 * N, dq), (R1, dq)]
+
+    def draw_keep_masks(self, R1, N, generator=None):
+        """One step's keep masks (uint8, 1 = kept with probability 1 - dropout), drawn on the device in one
+        ``bernoulli_``: [attention layer 0, attention layer 1, fc layer 0, fc layer 1]."""
+        shapes = self.keep_mask_shapes(R1, N)
+        sizes = [int(np.prod(sh)) for sh in shapes]
+        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=self._dev()).bernoulli_(
+            1.0 - float(self.embedding_module.dropout), generator=generator)
+        return [x.view(sh) for x, sh in zip(flat.split(sizes), shapes)]
+
+    def _updated_state(self, dev):
+        """get_updated_memory(all nodes, messages) (tgn.py:241-252) from the device store: M' = memory with
+        GRUCell(mlp(last raw message), memory) on every node with a pending message, under autograd (memory and
+        the stored messages are constants; the gradient reaches the message MLP and the GRU cell).  The cell
+        runs over all nodes and ``where`` keeps the flagged rows: no host synchronisation, no compaction."""
+        mem = self.memory
+        if not mem.store_is_newer:
+            self.messages_from_dict(dev)        # memory.messages is what counts until the first stateful step
+        h = mem.memory.data
+        if not mem.store_any:
+            return dict(M=h)                    # nothing pending anywhere: the message MLP and the cell do not run
+        l0, l2 = self.message_function.mlp[0], self.message_function.mlp[2]
+        cell = self.memory_updater.memory_updater
+        msg = F.linear(F.relu(F.linear(mem.msg_raw, l0.weight, l0.bias)), l2.weight, l2.bias)
+        gi = F.linear(msg, cell.weight_ih, cell.bias_ih)
+        gh = F.linear(h, cell.weight_hh, cell.bias_hh)
+        ir, iz, inn = gi.chunk(3, 1)
+        hr, hz, hn = gh.chunk(3, 1)
+        r = torch.sigmoid(ir + hr)
+        z = torch.sigmoid(iz + hz)
+        n = torch.tanh(inn + r * hn)
+        M = torch.where(mem.msg_flag.unsqueeze(1), (h - n) * z + n, h)
+        return dict(M=M)
+
+    def _layer_live(self, lay, tab, src_idx, R, N, node_idx, ngh_dense, edge_idx, edge_dense, dt, mask_node, seg,
+                    akeep, fkeep, scale, tw, tb, cosb):
+        """_layer on the live parameters with both dropouts of MultiHeadAttention -> [R, d_node]."""
+        mh = lay.multi_head_target
+        H, dk = mh.n_head, mh.d_k
+        dn = self.n_node_features
+        dq = 2 * dn
+        if H > 4:
+            raise NotImplementedError(f"n_heads {H}: the attention kernels hold at most 4 heads")
+        if tab.requires_grad:
+            src = _GatherRowsFn.apply(tab, src_idx, self._live_err)
+        else:
+            src = tab.index_select(0, src_idx)
+        query = torch.cat([src, cosb.expand(R, dn)], dim=1)                           # [R, dq]
+        wq = mh.w_qs.weight.view(H, dk, dq)
+        wk, wv = mh.w_ks.weight.view(H, dk, dk), mh.w_vs.weight.view(H, dk, dk)
+        P = torch.einsum("hoi,hoq->hiq", wk, wq).reshape(H * dk, dq)                   # W_k,h^T W_q,h
+        G = torch.einsum("qho,hoi->qhi", mh.fc.weight.view(dq, H, dk), wv).reshape(dq, H * dk)
+        qf = (query @ P.t()).contiguous()
+        de = edge_dense.shape[-1] if edge_dense is not None else self.n_edge_features
+        if dn + de + dn != dk:
+            raise AssertionError(f"key dim {dn}+{de}+{dn} != {dk}")
+        spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=dn, d_edge=de, d_time=dn,
+                    node_rows=tab.shape[0], edge_rows=self.e_feat_th.shape[0], head_major=self.head_major_rows,
+                    temperature=mh.temperature, node_idx=node_idx,
+                    edge_tab=edge_dense if edge_dense is not None else self.e_feat_th,
+                    edge_idx=None if edge_dense is not None else edge_idx, dt=dt, mask_node=mask_node,
+                    err=self._live_err, seg_rows=seg)
+        z = _TgnTrainAttnFn.apply(qf, ngh_dense, None if ngh_dense is not None else tab, tw, tb, spec, akeep, scale)
+        out = torch.addmm(mh.fc.bias, z, G.t())
+        if fkeep is not None:
+            out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (embedding_module.py:84)
+        h = F.layer_norm(out + query, (dq,), mh.layer_norm.weight, mh.layer_norm.bias, 1e-5)
+        return lay.merger(h, src)
+
+    def _embed_live(self, x, st, explain_weights=None, edge_attr=None):
+        """embedding_update_layer over tab = M' + n_feat on the live parameters (the training pair; without
+        keep masks in eval() / under no_grad, where its bits are the plain kernels')."""
+        if explain_weights is not None:
+            raise NotImplementedError("TGN with memory updates: explain_weights (the explainer runs on the frozen "
+                                      "model, forbidden_memory_update=True)")
+        train = self.training and torch.is_grad_enabled()
+        if train and not getattr(self, "_train_on_hip", False):
+            raise NotImplementedError("TGN in train() mode with memory updates: call model.train_on_hip() first "
+                                      "(the HIP training step is opt-in; eval() / no_grad need no flag)")
+        R1, N, seg1 = x["R1"], x["N"], x["seg1"]
+        p = float(self.embedding_module.dropout) if train else 0.0
+        dev = st["M"].device
+        keep = getattr(self, "tgn_keep_masks", None) if train else None
+        if keep is None and p > 0.0:
+            keep = self.draw_keep_masks(R1, N)
+        if keep is not None:
+            shapes = self.keep_mask_shapes(R1, N)
+            if len(keep) != 4 or any(k.dtype != torch.uint8 or k.device != dev or k.numel() != int(np.prod(sh))
+                                     for k, sh in zip(keep, shapes)):
+                raise ValueError("TGN.tgn_keep_masks: expected draw_keep_masks(R1, N)'s four uint8 masks on the device")
+            keep = [k.contiguous().view(sh) for k, sh in zip(keep, shapes)]
+        else:
+            keep = [None] * 4
+        scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+        tab = (st["M"] + self.n_feat_th).contiguous()
+        te = self.time_encoder
+        tw, tb = te.w.weight.view(-1), te.w.bias
+        cosb = torch.cos(tb)
+        lay0, lay1 = self.embedding_module.attention_models[0], self.embedding_module.attention_models[1]
+        # layer 0: hop-1 nodes attend over their hop-2 neighbours, keys gathered from tab
+        y0 = self._layer_live(lay0, tab, x["n1l"], R1 * N, N, x["n2f"], None, x["e2"], x["ed2"], x["dt2"], x["n2f"],
+                              seg1 * N, keep[0], keep[2], scale, tw, tb, cosb)
+        # layer 1: roots attend over the hop-1 embeddings
+        y1 = self._layer_live(lay1, tab, x["n0"], R1, N, None, y0.contiguous(), x["e1"], x["ed1"], x["dt1"],
+                              x["n1f"], seg1, keep[1], keep[3], scale, tw, tb, cosb)
+        self._tgn_train_key = (R1, N, keep[0] is not None)   # marker: the stateful path ran
+        return y1
+
+    def _stateful_embed(self, x, src_idx, tgt_idx, cut_time, e_idx, explain_weights=None, edge_attr=None):
+        """get_node_emb with memory updates (tgn.py:123-196): embeddings over the updated memory, then the state
+        moves on with this step's values (no gradient flows into the stored state)."""
+        dev = self._live_dev()
+        st = self._updated_state(dev)
+        emb = self._embed_live(x, st, explain_weights, edge_attr)
+        if len(src_idx) > 0:
+            with torch.no_grad():
+                self._advance_state(st["M"].detach(), emb.detach(), src_idx, tgt_idx, cut_time, e_idx, dev)
+        return emb
+
+    def _advance_state(self, M, emb, src_idx, tgt_idx, cut_time, e_idx, dev):
+        """tgn.py:167-191 on the device, without a loop over events or nodes and without a host synchronisation:
+        persist the positives' updated memory and clear their messages, then store this batch's raw messages.
+        Of a node's messages the ``last`` aggregator reads the last one: source-role messages are appended before
+        destination-role ones, each in batch order, so the winner is the entry with the largest index in
+        [src | dst] -- read off a stable sort, never off a scatter with duplicate indices."""
+        mem = self.memory
+        if e_idx is None:
+            raise ValueError("TGN with memory updates: e_idx is needed for the raw messages")
+        B, n = len(src_idx), self.n_nodes
+        src = _as_dev(src_idx, dev, torch.long).reshape(-1)
+        dst = _as_dev(tgt_idx, dev, torch.long).reshape(-1)
+        pos = torch.cat([src, dst])
+        vals, order = torch.sort(pos, stable=True)
+        ar = torch.arange(n, dtype=torch.long, device=dev)
+        hi = torch.searchsorted(vals, ar, right=True)
+        is_pos = hi > torch.searchsorted(vals, ar)
+        sel = order[(hi - 1).clamp_min(0)]                  # a positive's last entry in [src | dst]
+        # update_memory(positives): only positives with a pending message change
+        apply = is_pos & mem.msg_flag
+        mem.memory.data = torch.where(apply.unsqueeze(1), M, mem.memory.data)
+        mem.last_update.data = torch.where(apply, mem.msg_ts, mem.last_update.data)
+        # get_raw_messages (:254-278) with the just updated last_update and ts cast to fp32
+        ts = _as_dev(cut_time, dev, torch.float64).reshape(-1)[:B].float()
+        lu = mem.last_update.data
+        ef = self.e_feat_th.index_select(0, _as_dev(e_idx, dev, torch.long).reshape(-1))
+        w64, b64 = self.time_encoder.w.weight.detach().view(1, -1).double(), self.time_encoder.w.bias.detach().double()
+
+        def tenc(delta):
+            # Linear(1, d) rounds dt*w + b once (an fma): the exact fp64 product and sum, rounded to fp32
+            return torch.cos((delta.double().unsqueeze(1) * w64 + b64).float())
+        s_emb, d_emb = emb[:B], emb[B:2 * B]
+        msgs = torch.cat([torch.cat([s_emb, d_emb, ef, tenc(ts - lu[src])], dim=1),
+                          torch.cat([d_emb, s_emb, ef, tenc(ts - lu[dst])], dim=1)])
+        ts2 = torch.cat([ts, ts])
+        mem.msg_raw = torch.where(is_pos.unsqueeze(1), msgs.index_select(0, sel), mem.msg_raw)
+        mem.msg_ts = torch.where(is_pos, ts2[sel], mem.msg_ts)
+        mem.msg_flag = mem.msg_flag | is_pos
+        mem.store_is_newer = mem.store_any = True
+        mem.messages = defaultdict(list)       # stale from here on; messages_to_dict() rebuilds it
+
+    def messages_from_dict(self, dev=None):
+        """memory.messages -> the device store: of every node's list the last (raw message, timestamp)."""
+        if self.aggregator_type != "last":
+            raise NotImplementedError(f"aggregator_type {self.aggregator_type!r}: the device store keeps a node's "
+                                      "last message only ('mean' reads them all)")
+        dev = dev or self._dev()
+        mem = self.memory
+        mem.ensure_store(self._raw_dim(), dev)
+        mem.msg_flag = torch.zeros_like(mem.msg_flag)
+        nodes = [int(k) for k, v in mem.messages.items() if len(v) > 0]
+        if nodes:
+            last = [mem.messages[k][-1] for k in nodes]
+            idx = torch.tensor(nodes, dtype=torch.long, device=dev)
+            raw = torch.stack([m[0].detach().to(dev, torch.float32) for m in last])
+            ts = torch.stack([torch.as_tensor(m[1]).detach().to(dev, torch.float32).reshape(()) for m in last])
+            mem.msg_raw = mem.msg_raw.index_copy(0, idx, raw)
+            mem.msg_ts = mem.msg_ts.index_copy(0, idx, ts)
+            mem.msg_flag = mem.msg_flag.index_fill(0, idx, True)
+        mem.store_is_newer, mem.store_any = False, bool(nodes)
+        return self
+
+    def pending_messages(self):
+        """{"nodes" [K] int64, "raw" [K, raw_dim], "ts" [K]}: the nodes with a pending message, ascending, and
+        their last raw message and its timestamp (synchronises)."""
+        mem = self.memory
+        if not mem.store_is_newer:
+            self.messages_from_dict()
+        nodes = torch.nonzero(mem.msg_flag).reshape(-1)
+        return {"nodes": nodes, "raw": mem.msg_raw.index_select(0, nodes), "ts": mem.msg_ts.index_select(0, nodes)}
+
+    def load_pending_messages(self, saved, dev=None):
+        """pending_messages()'s dict (as learn_base saves it next to the state_dict) -> the device store."""
+        dev = dev or self._dev()
+        mem = self.memory
+        mem.ensure_store(self._raw_dim(), dev)
+        idx = saved["nodes"].to(dev, torch.long)
+        mem.msg_raw = torch.zeros_like(mem.msg_raw).index_copy(0, idx, saved["raw"].to(dev, torch.float32))
+        mem.msg_ts = torch.zeros_like(mem.msg_ts).index_copy(0, idx, saved["ts"].to(dev, torch.float32))
+        mem.msg_flag = torch.zeros_like(mem.msg_flag).index_fill(0, idx, True)
+        mem.store_is_newer, mem.store_any = True, idx.numel() > 0
+        mem.messages = defaultdict(list)
+        return self
+
+    def messages_to_dict(self):
+        """The device store -> memory.messages (what the frozen path and the reference's methods read): one
+        (raw message, timestamp) entry per node with a pending message."""
+        mem = self.memory
+        if not mem.store_is_newer:
+            return self                          # memory.messages is what counts already
+        out = defaultdict(list)
+        if mem.msg_flag is not None:
+            nodes = torch.nonzero(mem.msg_flag).reshape(-1)
+            raw, ts = mem.msg_raw.index_select(0, nodes), mem.msg_ts.index_select(0, nodes)
+            for i, k in enumerate(nodes.tolist()):
+                out[k] = [(raw[i], ts[i])]
+        mem.messages = out
+        mem.store_is_newer = False
+        return self
+
     # -------------------------------------------------------------- forward pieces
     def _layer(self, pk, li, src_feat, R, N, node_idx, ngh_dense, edge_idx, edge_dense, dt, mask_node, ew, seg=0,
                cache=None):
@@ -497,9 +924,11 @@ class TGN(nn.Module):
         gives the same result as in its own call (the head-major pairing stays inside its batch).
         ``prepared``: the output of ``_prep_inputs`` for these inputs (built once when the same
         subgraphs go through several contrasts, as the training step's two do)."""
-        if self.use_memory and not self.forbidden_memory_update:
-            raise NotImplementedError("stateful memory updates inside contrast (tgn.py:167-199) are not part of "
-                                      "this build; set forbidden_memory_update=True as temp_exp_main.py:704 does")
+        if self._stateful():
+            x = prepared if prepared is not None else self._prep_inputs(nodes, eids, times, cut_time, edge_attr,
+                                                                        n_segments)
+            # no events here: the embeddings over the updated memory, the state left as it is
+            return self._embed_live(x, self._updated_state(self._live_dev()), explain_weights, edge_attr)
         pk = self._pack()
         x = prepared if prepared is not None else self._prep_inputs(nodes, eids, times, cut_time, edge_attr, n_segments)
         R1, N, seg1 = x["R1"], x["N"], x["seg1"]
@@ -554,19 +983,24 @@ class TGN(nn.Module):
     def check_errors(self):
         """Raise if a kernel saw an out-of-range node or edge index (synchronises)."""
         pk = self._pack_cache
-        if pk is not None and int(pk["err"].item()) != 0:
-            pk["err"].zero_()
-            raise IndexError("TGN: node or edge index out of range of the feature tables")
+        for err in ((pk or {}).get("err"), getattr(self, "_live_err", None)):
+            if err is not None and int(err.item()) != 0:
+                err.zero_()
+                raise IndexError("TGN: node or edge index out of range of the feature tables")
 
     # -------------------------------------------------------------- reference API
     def get_node_emb(self, src_idx, tgt_idx, bgd_idx, cut_time, e_idx, subgraph_src, subgraph_tgt, subgraph_bgd,
                      explain_weights=None, edge_attr=None, prepared=None):
         """tgn.py:99-199 -> (source, destination, negative) embeddings [B, d] each."""
         B = len(src_idx)
+        stateful = self._stateful()
         if prepared is None:
             prepared = self.prepare_contrast(src_idx, tgt_idx, bgd_idx, cut_time, subgraph_src, subgraph_tgt,
                                              subgraph_bgd, edge_attr)
-        emb = self.node_embeddings(None, None, None, None, explain_weights, edge_attr, prepared=prepared)
+        if stateful:
+            emb = self._stateful_embed(prepared, src_idx, tgt_idx, cut_time, e_idx, explain_weights, edge_attr)
+        else:
+            emb = self.node_embeddings(None, None, None, None, explain_weights, edge_attr, prepared=prepared)
         # split (one backward: a cat of the three gradients) rather than three slices (a zero-filled full-size
         # gradient, a copy and an add each)
         return tuple(emb.split(B)) if B > 0 else (emb[:0], emb[:0], emb[:0])
@@ -601,16 +1035,23 @@ class TGN(nn.Module):
         """tgn.py:201-218 -> (pos_score [B,1], neg_score [B,1]).  ``prepared``: prepare_contrast's
         output for these same inputs (optional, shared by several contrasts of one batch)."""
         B = len(src_idx)
+        stateful = self._stateful()
         if prepared is None:
             prepared = self.prepare_contrast(src_idx, tgt_idx, bgd_idx, cut_time, subgraph_src, subgraph_tgt,
                                              subgraph_bgd, edge_attr)
-        emb = self.node_embeddings(None, None, None, None, explain_weights, edge_attr, prepared=prepared)
+        if stateful:
+            emb = self._stateful_embed(prepared, src_idx, tgt_idx, cut_time, e_idx, explain_weights, edge_attr)
+        else:
+            emb = self.node_embeddings(None, None, None, None, explain_weights, edge_attr, prepared=prepared)
         if B == 0:
             return emb[:0, :1], emb[:0, :1]
         # get_node_emb's (s, d, n) as two pieces of one split: [d; n] is emb's tail (no copy), and the backward
         # is one cat instead of a zero-filled full-size gradient, a copy and an add per slice
         s, dn = emb.split([B, 2 * B])
-        score = self.affinity(torch.cat([s, s], dim=0), dn).squeeze(dim=0)
+        if stateful:
+            score = self.affinity_score(torch.cat([s, s], dim=0), dn).squeeze(dim=0)      # the live parameters
+        else:
+            score = self.affinity(torch.cat([s, s], dim=0), dn).squeeze(dim=0)
         return tuple(score.split(B))
 
     def retrieve_edge_features(self, subgraph_src, subgraph_tgt, subgraph_bgd):

@@ -99,13 +99,13 @@ def beta_mean(p):
 
 def edge_importance(sd, e_feat, imp, walk_eid, walk_ts, sub_node, sub_eid, dependency=True):
     """retrieve_edge_imp_node, eval (explainer_new.py:354-406).  sub_*: [hop1 [B,N], hop2 [B,N^2]].
-    dependency=False: use_dependency_aware_sampling=False (no gate, :366-386 skipped)."""
+    dependency=False: use_dependency_aware_sampling=False (no gate, :366-386 skipped).  Computes in imp's dtype."""
     B = imp.shape[0]
     ew = torch.as_tensor(np.asarray(walk_eid), dtype=torch.long).reshape(B, -1)
     tw = torch.as_tensor(np.asarray(walk_ts, dtype=np.float64)).float().reshape(B, -1)
     wimp = imp.repeat(1, 1, 3).view(B, -1)
     if dependency:
-        g = torch.cat([e_feat[ew], time_encode(sd, tw)], dim=-1)
+        g = torch.cat([e_feat.to(imp.dtype)[ew], time_encode(sd, tw)], dim=-1)
         g = torch.relu(_lin(sd, "edge_dependency_gcn.0", g))
         g = torch.relu(_lin(sd, "edge_dependency_gcn.3", g))
         g = _lin(sd, "edge_dependency_gcn.6", g).squeeze(-1)
@@ -113,7 +113,7 @@ def edge_importance(sd, e_feat, imp, walk_eid, walk_ts, sub_node, sub_eid, depen
     i0 = torch.as_tensor(np.asarray(sub_eid[0]), dtype=torch.long)
     i1 = torch.as_tensor(np.asarray(sub_eid[1]), dtype=torch.long)
     n_e = int(max(ew.max(), i0.max(), i1.max()) + 1)
-    dense = torch.zeros(B, n_e).scatter_reduce(-1, ew, wimp, "amax", include_self=False)
+    dense = torch.zeros(B, n_e, dtype=wimp.dtype).scatter_reduce(-1, ew, wimp, "amax", include_self=False)
     outs = []
     for idx, nd in ((i0, sub_node[0]), (i1, sub_node[1])):
         v = beta_mean(torch.gather(dense, -1, idx))

@@ -199,6 +199,19 @@ __device__ __forceinline__ int32_t draw(Key k, uint32_t stage, uint32_t event, u
     return (int32_t)(((uint64_t)u * (uint64_t)high) >> 32);
 }
 
+// TimeEncode's argument t w + b with the product and the sum rounded separately, as torch computes it (the
+// explainer's TimeEncode.forward, explainer_new.py:56-58, and TGAT.py:236-237: a multiply, then an add).  The
+// contraction is switched off for this block: hipcc's default -ffp-contract=fast turns a product-sum into one
+// v_fma_f32 / v_fmac_f32, also when it is spelled __fadd_rn(__fmul_rn(t, w), b) (plain * and + in this
+// toolchain's headers), and at arguments of 1e5 .. 1e8 the single rounding moves the cosine by up to 3e-2
+// whenever b != 0.  Every time feature of the explainer and of TGAT, and the temporal attention's
+// 0.3 tw + 0.7 multiplier, goes through here.
+__device__ __forceinline__ float time_arg(float t, float w, float b) {
+#pragma clang fp contract(off)
+    const float p = t * w;
+    return p + b;
+}
+
 // cos of an fp32 argument, branch-free: the argument in revolutions, x / (2 pi), reduced to [-1/2, 1/2]
 // in fp64 (relative error 2^-53: |x| < 2^40 keeps the reduced fraction exact to ~1e-9), then the
 // hardware v_cos_f32 (input in revolutions).  Max abs error vs cos of the same fp32 argument 1.8e-7

@@ -318,7 +318,7 @@ __global__ void __launch_bounds__(256) head_kernel(EncW P, int64_t n_walks, int6
         s += __shfl_xor(s, 2, 4);
         if (sub == 0 && w < TR) {
             // scores * (1.0 - 0.3 + 0.3 * time_weight)   (:835-836)
-            const float m = __fadd_rn(0.7f, __fmul_rn(0.3f, s_tw[pair]));
+            const float m = tw_mult(s_tw[pair]);
             s_score[pair] = s * m;
         }
     }
@@ -1339,8 +1339,8 @@ __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsr
         tw1 = expf(-fabsf(cu - (hi.v ? hi.t1 : 0.f)) / sd);
     }
     // scores * (1.0 - 0.3 + 0.3 * time_weight) (:835-836), softmax over the 2 targets
-    s0 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw0));
-    s1 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw1));
+    s0 *= tw_mult(tw0);
+    s1 *= tw_mult(tw1);
     const float mx = fmaxf(s0, s1), e0 = expf(s0 - mx), e1 = expf(s1 - mx), sum = e0 + e1;
     const float al0 = e0 / sum, al1 = e1 / sum;
     // alpha is uniform over a column's 4 lane groups (score_dot ends in col_sum): Hm is in H's layout
@@ -1401,8 +1401,8 @@ __device__ __forceinline__ void walk_pool_head(const WalkArgs &a, __amdgpu_buffe
         tw0 = expf(-fabsf(cu - (hi.v ? hi.t0 : 0.f)) / sd);
         tw1 = expf(-fabsf(cu - (hi.v ? hi.t1 : 0.f)) / sd);
     }
-    s0 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw0));
-    s1 *= __fadd_rn(0.7f, __fmul_rn(0.3f, tw1));
+    s0 *= tw_mult(tw0);
+    s1 *= tw_mult(tw1);
     const float mx = fmaxf(s0, s1), e0 = expf(s0 - mx), e1 = expf(s1 - mx), sum = e0 + e1;
     const float al0 = e0 / sum, al1 = e1 / sum;
     floatx4 Hm[NA];

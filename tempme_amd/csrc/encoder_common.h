@@ -116,8 +116,13 @@ __device__ __forceinline__ int erow(int mt, int r) { return mt * 16 + 4 * ((thre
 __device__ __forceinline__ int ecol(int nt) { return nt * 16 + (threadIdx.x & 15); }
 
 // cos(t * w + phi) with the multiply and add rounded separately, as torch does
-// (TimeEncode.forward, explainer_new.py:56-58); never contracted into an fma.
-__device__ __forceinline__ float time_cos(float t, float w, float phi) { return cos_rd(__fadd_rn(__fmul_rn(t, w), phi)); }
+// (TimeEncode.forward, explainer_new.py:56-58); never contracted into an fma (time_arg, common.h).
+__device__ __forceinline__ float time_cos(float t, float w, float phi) { return cos_rd(time_arg(t, w, phi)); }
+// the derivative's sine at the same argument
+__device__ __forceinline__ float time_sin(float t, float w, float phi) { return sin_rd(time_arg(t, w, phi)); }
+// the temporal attention's score multiplier 1.0 - 0.3 + 0.3 * time_weight (explainer_new.py:835-836): 0.7 in
+// fp32, a rounded product, a rounded sum
+__device__ __forceinline__ float tw_mult(float tw) { return time_arg(0.3f, tw, 0.7f); }
 
 __device__ __forceinline__ float relu(float x) { return x > 0.f ? x : 0.f; }
 

@@ -355,7 +355,7 @@ __global__ void __launch_bounds__(256) head_bwd_kernel(EncW P, EncWT T, int64_t 
             const float c = (float)cut[g * (walks_per_group / W) + b];
             tw = expf(-fabsf(c - ts3[gw * 3 + p]) / (stdv[g] + 1e-6f));
         }
-        s_mult[tid] = P.tg ? __fadd_rn(0.7f, __fmul_rn(0.3f, tw)) : 1.f;   // 1.0 - 0.3 + 0.3 * time_weight (:835-836)
+        s_mult[tid] = P.tg ? tw_mult(tw) : 1.f;   // 1.0 - 0.3 + 0.3 * time_weight (:835-836)
     }
     if (!POOL && tid < TR) s_cat[tid] = valid(tid) ? cat[w0 + tid] : -1;
     __syncthreads();
@@ -742,7 +742,7 @@ __global__ void __launch_bounds__(256) gcn_bwd_kernel(EncW P, EncWT T, int64_t n
             const int row = erow(mt, r);
             if (!valid(row)) continue;
             float gv = 0.f;
-            if (j < dn) gv = -acc[r] * sinf(__fadd_rn(__fmul_rn(s_dt[row], P.freq[j]), P.phase[j]));
+            if (j < dn) gv = -acc[r] * sinf(time_arg(s_dt[row], P.freq[j], P.phase[j]));
             o.g[(row0 + row) * dn16 + j] = gv;
         }
     });
@@ -974,7 +974,7 @@ __device__ __forceinline__ void gcn_bwd_reg_zn(const EncW &P, const EncWT &T, co
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int j = 16 * t + 4 * g + s;
-                gv[s] = (t < NTD - 1 || j < dn) ? -GT[t][s] * sin_rd(__fadd_rn(__fmul_rn(dt, fv[s]), hv[s])) : 0.f;
+                gv[s] = (t < NTD - 1 || j < dn) ? -GT[t][s] * time_sin(dt, fv[s], hv[s]) : 0.f;
             }
             *reinterpret_cast<float4 *>(o.g + r * DN + 16 * t + 4 * g) = make_float4(gv[0], gv[1], gv[2], gv[3]);
         }
@@ -1091,7 +1091,7 @@ __global__ void __launch_bounds__(256, 2) gcn_bwd_reg_kernel(EncW P, EncWT T, in
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int j = 16 * t + 4 * g + s;
-                gv[s] = (t < NTD - 1 || j < dn) ? -GT[t][s] * sin_rd(__fadd_rn(__fmul_rn(dt, fv[s]), hv[s])) : 0.f;
+                gv[s] = (t < NTD - 1 || j < dn) ? -GT[t][s] * time_sin(dt, fv[s], hv[s]) : 0.f;
             }
             *reinterpret_cast<float4 *>(o.g + r * DN + 16 * t + 4 * g) = make_float4(gv[0], gv[1], gv[2], gv[3]);
         }
@@ -1565,7 +1565,7 @@ __global__ void __launch_bounds__(256) gate_train_bwd_kernel(EncW P, EncWT T, in
             const int row = erow(mt, r);
             if (!valid(row)) continue;
             float gv = 0.f;
-            if (j < dn) gv = -acc[r] * sinf(__fadd_rn(__fmul_rn(s_t[row], P.freq[j]), P.phase[j]));
+            if (j < dn) gv = -acc[r] * sinf(time_arg(s_t[row], P.freq[j], P.phase[j]));
             o.g[(r0 + row) * dn16 + j] = gv;
         }
     });

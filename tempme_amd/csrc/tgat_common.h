@@ -1,6 +1,6 @@
 // Device helpers shared by the TGAT attention kernels (tgat_attn.hip: the frozen base model; tgat_train.hip:
 // the training pair): the lane layout of a key, the on-the-fly key build with TGAT's two-rounding time
-// feature, the head-major pairing of mask / weight rows and the 64-lane butterfly sum.
+// feature (time_arg, common.h), the head-major pairing of mask / weight rows and the 64-lane butterfly sum.
 #pragma once
 #include "common.h"
 
@@ -14,16 +14,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-}
-
-// TimeEncode's argument t w + b with the product and the sum rounded separately (TGAT.py:236-237: a multiply,
-// then an in-place add).  The contraction is switched off for this block: hipcc's default -ffp-contract=fast
-// turns a product-sum into one v_fma_f32, also when it is spelled __fadd_rn(__fmul_rn(t, w), b) (plain * and +
-// in this toolchain's headers), and at arguments of 1e5 .. 1e6 the single rounding moves the cosine by up to 3e-2.
-__device__ __forceinline__ float time_arg(float t, float w, float b) {
-#pragma clang fp contract(off)
-    const float p = t * w;
-    return p + b;
 }
 
 template <int KPL>

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import phase_inputs as PI
 from oracle import encoder_ref as er
 
 pytestmark = pytest.mark.gpu
@@ -57,19 +58,37 @@ def _inputs(de, G, B, N, seed, zero_nodes=False):
 
 # de = 32 runs the register-resident event_gcn kernels (hid_dim 64, 4 | de), de = 1 the LDS-tiled ones; zn = zero
 # node features (both kernels' one-branch forms)
-@pytest.mark.parametrize("de,G,B,N,train,zn", [(32, 3, 20, 20, True, False), (1, 2, 7, 5, True, False),
-                                               (32, 1, 9, 20, False, False), (32, 3, 20, 20, True, True),
-                                               (32, 1, 9, 20, False, True), (1, 2, 7, 5, True, True),
-                                               (172, 2, 11, 20, True, False)])
+CASES = [(32, 3, 20, 20, True, False), (1, 2, 7, 5, True, False), (32, 1, 9, 20, False, False),
+         (32, 3, 20, 20, True, True), (32, 1, 9, 20, False, True), (1, 2, 7, 5, True, True),
+         (172, 2, 11, 20, True, False)]
+
+
+@pytest.mark.parametrize("de,G,B,N,train,zn", CASES)
 def test_encoder_backward_matches_autograd(dev, de, G, B, N, train, zn):
     """Forward within 1e-5 and all 22 gradients within 2e-4 of fp64 autograd through the oracle; zn: zero node
     features, i.e. gcn_kernel / gcn_bwd_kernel's one-branch forms and the summed MLP.0 / MLP.2 weight-gradient rows."""
+    _encoder_backward_case(dev, de, G, B, N, train, zn, 0.0)
+
+
+# The perturbed-phase legs (phase ~ N(0, 0.5), phase_inputs.py, in the explainer and in the oracle's state dict):
+# the constructor's zero phase, which the cases above keep under their test ids, cannot show a contracted time
+# argument t * w + phase, a wrong phase index or a wrong d phase.  Same cases, same bounds;
+# test_time_phase_cpu.py shows on the oracle that a single-rounding argument moves at least three of the 22
+# gradients by 1e-2 of their norm (50 times the bound) on these inputs.
+@pytest.mark.parametrize("de,G,B,N,train,zn", CASES)
+def test_encoder_backward_matches_autograd_perturbed_phase(dev, de, G, B, N, train, zn):
+    _encoder_backward_case(dev, de, G, B, N, train, zn, PI.SIGMA)
+
+
+def _encoder_backward_case(dev, de, G, B, N, train, zn, phase_sigma):
     from tempme_amd import TempME
     n_feat, e_feat, node6, eid3, ts3, cat, cut, cnt = _inputs(de, G, B, N, seed=de + G + B, zero_nodes=zn)
     W = 3 * N
     torch.manual_seed(7)
     ex = TempME(_Base(n_feat, e_feat), "tgn", "synth", 40, 64, device=dev,
                 null_model={k: 1 / 12 for k in range(1, 13)}).to(dev)
+    if phase_sigma:
+        PI.set_phase(ex, PI.perturbed_phase(ex.time_encoder.phase.numel(), phase_sigma))
     ex.train(train)
     ex.feature_tables()
     assert ex._node_zero == zn
@@ -113,6 +132,15 @@ VARIANTS = {"notg": dict(use_temporal_guidance=False), "nocat": dict(if_cat_feat
 
 @pytest.mark.parametrize("var", sorted(VARIANTS))
 def test_encoder_backward_variants_match_autograd(dev, var):
+    _encoder_variant_case(dev, var, 0.0)
+
+
+@pytest.mark.parametrize("var", sorted(VARIANTS))
+def test_encoder_backward_variants_match_autograd_perturbed_phase(dev, var):
+    _encoder_variant_case(dev, var, PI.SIGMA)
+
+
+def _encoder_variant_case(dev, var, phase_sigma, phase_seed=5):
     from tempme_amd import TempME
     kw = dict(hid_dim=64)
     kw.update(VARIANTS[var])
@@ -123,6 +151,8 @@ def test_encoder_backward_variants_match_autograd(dev, var):
     torch.manual_seed(5)
     ex = TempME(_Base(n_feat, e_feat), "tgn", "synth", 40, h, device=dev,
                 null_model={k: 1 / 12 for k in range(1, 13)}, **kw).to(dev)
+    if phase_sigma:
+        PI.set_phase(ex, PI.perturbed_phase(ex.time_encoder.phase.numel(), phase_sigma, phase_seed))
     ex.train(True)
     assert ex._hip_ok(), var
     tg, ic = ex.use_temporal_guidance, ex.if_cat

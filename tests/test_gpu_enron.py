@@ -144,10 +144,9 @@ def test_pipeline_matches_reference_enron(dev, finder, g, z, N, edge_table):
     np.testing.assert_allclose(h2.reshape(3 * E, N * N).cpu().numpy(), z[f"{tag}_expl1"], rtol=RTOL, atol=ATOL)
 
 
-def test_train_step_matches_reference_enron(dev, g, z):
-    """One deterministic iteration of the training loop (temp_exp_main.py:605-632, Explainer.eval(),
-    Beta mean) on the reference TGN at Enron dims and timestamps: losses, logits, every gradient that
-    reaches the explainer, and the Adam update."""
+def _golden_train_step(dev, g, z):
+    """The golden training iteration (make_goldens.py case_enron): -> (explainer after the step, train_step's
+    outputs, the parameters before it, the walks record of its N = 20 batch)."""
     from tempme_amd import TempME
     from tempme_amd.train import Batch, train_step
     N, B = 20, EI.SETS[20]
@@ -169,6 +168,14 @@ def test_train_step_matches_reference_enron(dev, g, z):
     p0 = {k: v.detach().clone() for k, v in ex.named_parameters()}
     ex.eval()
     out = train_step(ex, base, opt, batch, beta=0.5, prior_p=0.3, if_bern=False)
+    return ex, out, p0, d
+
+
+def test_train_step_matches_reference_enron(dev, g, z):
+    """One deterministic iteration of the training loop (temp_exp_main.py:605-632, Explainer.eval(),
+    Beta mean) on the reference TGN at Enron dims and timestamps: losses, logits, every gradient that
+    reaches the explainer, and the Adam update."""
+    ex, out, p0, _ = _golden_train_step(dev, g, z)
     got = np.array([out["loss"].item(), out["pred_loss"].item(), out["kl_loss"].item()])
     np.testing.assert_allclose(got, z["train_losses"], rtol=1e-5, atol=1e-6)
     logits = torch.cat([out["pos_logit"], out["neg_logit"]]).cpu().numpy()

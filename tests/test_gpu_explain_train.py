@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import phase_inputs as PI
 from oracle import encoder_ref as er
 
 pytestmark = pytest.mark.gpu
@@ -32,9 +33,9 @@ class _Base:
         self.edge_raw_features = torch.nn.Embedding.from_pretrained(self.e_feat_th, padding_idx=0, freeze=True)
 
 
-@pytest.mark.parametrize("de,G,B,N,train", [(32, 3, 12, 20, True), (1, 2, 5, 5, True), (32, 1, 7, 10, False)])
-def test_explain_backward_matches_autograd(dev, de, G, B, N, train):
-    from tempme_amd import TempME
+def _explain_inputs(de, G, B, N):
+    """Walk edges and absolute timestamps in [0, 1e6), subgraph slots and the loss weights of
+    test_explain_backward_matches_autograd (one seeded stream, in this order)."""
     rng = np.random.RandomState(de + B)
     V, E, W = 50, 400, 3 * N
     n_feat = rng.uniform(0, 1, (V + 1, 172)).astype(np.float32)
@@ -51,12 +52,40 @@ def test_explain_backward_matches_autograd(dev, de, G, B, N, train):
     s2e = rng.randint(0, E + 1, (G, B, N * N)).astype(np.int32)
     m2 = min(N * N // 2, 3 * W)
     s2e[..., :m2] = eid3.reshape(G, B, -1)[..., :m2]
-    s1n = rng.randint(0, 3, (G, B, N)).astype(np.int32)
-    s2n = rng.randint(0, 3, (G, B, N * N)).astype(np.int32)
+    rng.randint(0, 3, (G, B, N)), rng.randint(0, 3, (G, B, N * N))   # (two unused draws keep the stream's order)
     imp_np = rng.uniform(0.05, 0.95, (G, B, W)).astype(np.float32)
+    w1 = torch.from_numpy(rng.uniform(-1, 1, G * B * N).astype(np.float32))
+    w2 = torch.from_numpy(rng.uniform(-1, 1, G * B * N * N).astype(np.float32))
+    return n_feat, e_feat, eid3, ts3, s1e, s2e, imp_np, w1, w2
+
+
+# phase_sigma: TimeEncode's phase perturbed by N(0, sigma) (phase_inputs.py) in the explainer and in the oracle's
+# state dict; 0.0 is the constructor's zero phase, at which a contracted time argument t * w + phase cannot show.
+# test_time_phase_cpu.py shows on the oracle that at these timestamps (up to 1e6) a single-rounding argument moves
+# six of the eight gradients below by more than 1e-2 of their norm, 500 times the fp32 bound.
+CASES = [(32, 3, 12, 20, True), (1, 2, 5, 5, True), (32, 1, 7, 10, False)]
+
+
+@pytest.mark.parametrize("de,G,B,N,train", CASES)
+def test_explain_backward_matches_autograd(dev, de, G, B, N, train):
+    _explain_backward_case(dev, de, G, B, N, train, 0.0)
+
+
+@pytest.mark.parametrize("de,G,B,N,train", CASES)
+def test_explain_backward_matches_autograd_perturbed_phase(dev, de, G, B, N, train):
+    """The same cases and bounds with phase ~ N(0, 0.5) (the zero-phase leg above keeps its test ids)."""
+    _explain_backward_case(dev, de, G, B, N, train, PI.SIGMA)
+
+
+def _explain_backward_case(dev, de, G, B, N, train, phase_sigma):
+    from tempme_amd import TempME
+    W = 3 * N
+    n_feat, e_feat, eid3, ts3, s1e, s2e, imp_np, w1, w2 = _explain_inputs(de, G, B, N)
     torch.manual_seed(9)
     ex = TempME(_Base(n_feat, e_feat), "tgn", "synth", 40, 64, device=dev,
                 null_model={k: 1 / 12 for k in range(1, 13)}).to(dev)
+    if phase_sigma:
+        PI.set_phase(ex, PI.perturbed_phase(ex.time_encoder.phase.numel(), phase_sigma))
     ex.train(train)
     R = G * B * 3 * W
     masks = ex.gate_dropout_masks(R)
@@ -67,8 +96,6 @@ def test_explain_backward_matches_autograd(dev, de, G, B, N, train):
     from tempme_amd.explainer import _ExplainFn
     p, _ = _ExplainFn.apply(ex, args, imp.reshape(-1), *ex._gate_params())
     p1, p2 = p[:G * B * N], p[G * B * N:]
-    w1 = torch.from_numpy(rng.uniform(-1, 1, G * B * N).astype(np.float32))
-    w2 = torch.from_numpy(rng.uniform(-1, 1, G * B * N * N).astype(np.float32))
     ((p1 * w1.to(dev)).sum() + (p2 * w2.to(dev)).sum()).backward()
     named = dict(ex.named_parameters())
     got = {k: named[k].grad.detach().cpu().double() for k in GATE}

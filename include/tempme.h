@@ -201,6 +201,14 @@ int tm_weights_free(tm_weights *w);
  * through as its high part alone (mid = lo = 0). */
 void tm_weight_split3(const float *in, int64_t n, uint16_t *hi, uint16_t *mid, uint16_t *lo);
 
+/* The split pack of event_gcn's first layer that the zero-node walk kernel multiplies with on bf16 MFMA, built on
+ * the host exactly as tm_weights_pack builds it on the device, from a row-major w[nout][dn].  With
+ * nt = ceil(nout / 16) output tiles and ns = ceil(ceil(dn / 16) / 2) pair steps, out holds nt * ns * 3 fragments of
+ * 512 bf16 bit patterns: fragment ((t * ns + u) * 3 + part) (part 0 / 1 / 2 = hi / mid / lo of tm_weight_split3),
+ * element lane * 8 + j = w[16 t + (lane & 15)][16 (2 u + (j >> 2)) + 4 (lane >> 4) + (j & 3)], zero where the row
+ * is >= nout or the column >= dn. */
+void tm_weight_gcn_split(const float *w, int32_t nout, int32_t dn, uint16_t *out);
+
 /* Workspace bytes tm_encoder_fwd needs for n_walks walks. */
 int64_t tm_encoder_workspace_bytes(const tm_weights *w, int64_t n_walks);
 

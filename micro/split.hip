@@ -290,6 +290,160 @@ static void run_lin_ev(const char *name, const void *w, float *out, int blocks, 
            flop / ms / 1e9, ms * 1e6 / iters);
 }
 
+// ---- event_gcn-shaped case (zero-node form): H[4 tiles] = bias + G1 relu(L) over K = 176 (11 input tiles in the D-tile
+// lane order the previous layer leaves them in), weight fragments streamed from L2, 2 waves per SIMD.  MODE 0:
+// v_mfma_f32_16x16x4_f32, 11 K steps, a step's 4 fragments two steps ahead (walk_kernel's form before the split);
+// MODE 6: v_mfma_f32_16x16x32_bf16 over 6 pair steps of two input tiles (the B operand split in registers from the
+// tile pair, the second half of the last step zero), six products per (tile, step), tile pairs interleaved, all 72
+// fragments streamed through a 12-deep ring; MODE 7: the same with the first 3 pair steps' 36 fragments resident in
+// LDS (copied once per workgroup), streamed and resident steps alternating.
+constexpr int evg_step(int k, int gl, int ns) {
+    const int nstr = ns - gl, m = nstr < gl ? nstr : gl;
+    if (k < 2 * m) return (k & 1) ? k / 2 : gl + k / 2;
+    return nstr > gl ? gl + k - m : k - m;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(256, 2) ev_gcn(const void *w, int iters, float *out) {
+    constexpr int NT = 11, NS = 6, GL = MODE == 7 ? 3 : 0;
+    __shared__ float4 gl[MODE == 7 ? GL * 12 * 64 : 1];
+    extern __shared__ float lds_pad[];   // sized by the launch so that two workgroups fill a CU (2 waves per SIMD)
+    if (threadIdx.x == 0) lds_pad[0] = 0.f;
+    if constexpr (MODE == 7) {
+        for (int i = threadIdx.x; i < GL * 12 * 64; i += blockDim.x) {
+            const int f = i >> 6, l = i & 63;
+            gl[i] = reinterpret_cast<const float4 *>(w)[((((f / 3) % 4) * NS + f / 12) * 3 + f % 3) * 64 + l];
+        }
+        __syncthreads();
+    }
+    floatx4 H[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) H[t] = floatx4{1e-3f * t, 1e-3f, 2e-3f, 3e-3f};
+#pragma nounroll
+    for (int it = 0; it < iters; ++it) {
+        floatx4 L[NT];
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            const float c = 1e-3f * (float)(q - 5);
+            L[q] = floatx4{H[q & 3][0] + c, H[q & 3][1] - c, H[q & 3][2] + c, H[q & 3][3] - c};
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) H[t] = floatx4{1e-3f, 2e-3f, 3e-3f, 4e-3f};
+        if constexpr (MODE == 0) {
+            const float4 *wp = reinterpret_cast<const float4 *>(w) + lane_id();
+            float4 wz[3][4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                wz[0][t] = wp[(t * NT + 0) * 64];
+                wz[1][t] = wp[(t * NT + 1) * 64];
+            }
+#pragma unroll
+            for (int q = 0; q < NT; ++q) {
+                if (q + 2 < NT) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) wz[(q + 2) % 3][t] = wp[(t * NT + q + 2) * 64];
+                }
+                floatx4 A;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) A[r] = 0.f + fmaxf(0.f + L[q][r], 0.f);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) H[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].x, A.x, H[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) H[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].y, A.y, H[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) H[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].z, A.z, H[t], 0, 0, 0);
+#pragma unroll
+                for (int t = 0; t < 4; ++t) H[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].w, A.w, H[t], 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+            const float4 *wp = reinterpret_cast<const float4 *>(w) + lane_id();
+            const int ln = lane_id();
+            constexpr int N = (NS - GL) * 12, D = 12;
+            auto off = [](int i) { return ((((i / 3) % 4) * NS + GL + i / 12) * 3 + i % 3) * 64; };
+            float4 buf[D];
+#pragma unroll
+            for (int i = 0; i < D; ++i) buf[i] = wp[off(i)];
+            auto take = [&](int i) {
+                const float4 a = buf[i % D];
+                if (i + D < N) buf[i % D] = wp[off(i + D)];
+                return a;
+            };
+            auto fetch = [&](int p, float4 (&f)[6]) {
+                const int u = evg_step(p / 2, GL, NS), t = 2 * (p & 1);
+#pragma unroll
+                for (int k = 0; k < 6; ++k) {
+                    if (u < GL) f[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
+                    else f[k] = take(((u - GL) * 4 + t) * 3 + k);
+                }
+            };
+            auto act = [&](float (&v)[8], int u, int j) {
+                const int q = 2 * u + (j >> 2);
+                v[j] = q < NT ? 0.f + fmaxf(0.f + L[q < NT ? q : 0][j & 3], 0.f) : 0.f;
+            };
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) act(v, evg_step(0, GL, NS), j);
+            Split3 xb = split8(v);
+            float4 wb[2][6];
+            fetch(0, wb[0]);
+#pragma unroll
+            for (int k = 0; k < NS; ++k) {
+                float vn[8] = {};
+#pragma unroll
+                for (int t = 0; t < 4; t += 2) {
+                    const int pp = 2 * k + t / 2;
+                    if (pp + 1 < 2 * NS) fetch(pp + 1, wb[(pp + 1) & 1]);
+                    const float4(&f)[6] = wb[pp & 1];
+                    const bf16x8 h0 = __builtin_bit_cast(bf16x8, f[0]), m0 = __builtin_bit_cast(bf16x8, f[1]),
+                                 l0 = __builtin_bit_cast(bf16x8, f[2]), h1 = __builtin_bit_cast(bf16x8, f[3]),
+                                 m1 = __builtin_bit_cast(bf16x8, f[4]), l1 = __builtin_bit_cast(bf16x8, f[5]);
+                    H[t] = MF(l0, xb.h, H[t]); H[t + 1] = MF(l1, xb.h, H[t + 1]);
+                    H[t] = MF(h0, xb.l, H[t]); H[t + 1] = MF(h1, xb.l, H[t + 1]);
+                    H[t] = MF(m0, xb.m, H[t]); H[t + 1] = MF(m1, xb.m, H[t + 1]);
+                    H[t] = MF(m0, xb.h, H[t]); H[t + 1] = MF(m1, xb.h, H[t + 1]);
+                    H[t] = MF(h0, xb.m, H[t]); H[t + 1] = MF(h1, xb.m, H[t + 1]);
+                    H[t] = MF(h0, xb.h, H[t]); H[t + 1] = MF(h1, xb.h, H[t + 1]);
+                    if (k + 1 < NS) {
+#pragma unroll
+                        for (int j = 2 * t; j < 2 * t + 4; ++j) act(vn, evg_step(k + 1, GL, NS), j);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (k + 1 < NS) xb = split8(vn);
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            H[t] = floatx4{fmaxf(H[t][0], 0.f), fmaxf(H[t][1], 0.f), fmaxf(H[t][2], 0.f), fmaxf(H[t][3], 0.f)};
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sum += H[t][0] + H[t][1] + H[t][2] + H[t][3];
+    out[blockIdx.x * blockDim.x + threadIdx.x] = sum;
+}
+
+template <int MODE>
+static void run_ev_gcn(const char *name, const void *w, float *out, int blocks, int iters) {
+    const int lds = (MODE == 7 ? 24 : 60) * 1024;
+    ev_gcn<MODE><<<blocks, 256, lds>>>(w, iters, out);
+    hipDeviceSynchronize();
+    hipEvent_t a, b;
+    hipEventCreate(&a);
+    hipEventCreate(&b);
+    hipEventRecord(a);
+    const int reps = 5;
+    for (int r = 0; r < reps; ++r) ev_gcn<MODE><<<blocks, 256, lds>>>(w, iters, out);
+    hipEventRecord(b);
+    hipEventSynchronize(b);
+    float ms;
+    hipEventElapsedTime(&ms, a, b);
+    ms /= reps;
+    const double flop = 2.0 * 176 * 64 * 16 * (double)iters * blocks * 4;   // fp32-equivalent
+    printf("event_gcn %-24s %.3f ms  %.1f TFLOP/s (fp32-equivalent), %.0f ns per 16-column pass\n", name, ms,
+           flop / ms / 1e9, ms * 1e6 / iters);
+}
+
 int main() {
     void *w;
     const size_t bytes = 4 * 8 * 4 * 3 * 64 * 16;   // 4 layers, bf16x3 packing (largest)
@@ -308,5 +462,8 @@ int main() {
     }
     run_lin_ev<0>("f32 16x16x4", w, out, blocks, 200);
     run_lin_ev<6>("bf16x3 6-prod", w, out, blocks, 200);
+    run_ev_gcn<0>("f32 16x16x4", w, out, blocks, 600);
+    run_ev_gcn<6>("bf16x3 6-prod streamed", w, out, blocks, 600);
+    run_ev_gcn<7>("bf16x3 6-prod half in LDS", w, out, blocks, 600);
     return 0;
 }

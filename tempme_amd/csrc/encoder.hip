@@ -642,9 +642,26 @@ struct WalkLay {
 // in the same order (the results do not change).
 constexpr int PFP = 4;     // weight-fragment ring depth (2, 4, 6 measured: 4 best)
 // waves per SIMD walk_kernel is compiled for, and waves per workgroup (each wave owns its 16 slots and a
-// 12.25 KB LDS stash, the workgroup one constant table; 3 waves per SIMD and 8-wave workgroups measured slower)
+// 12.25 KB LDS stash -- 8.25 KB in the zero-node form --, the workgroup one constant table; 3 waves per SIMD and
+// 8-wave workgroups measured slower)
 constexpr int WALK_WAVES = 2;
 constexpr int WALK_WPB = 4;
+
+// Zero-node instances: event_gcn's first layer runs on bf16 MFMA off the split pack EncW::g13 (pair steps of two
+// input tiles), and GCN_LDS of its pair steps are resident in LDS -- copied once per workgroup at kernel start into
+// the room the zero-node stash leaves (36 KB: 2 workgroups per CU still fit) -- while the rest stream from L2.  The
+// kernel sits at the rate a CU takes weight fragments in from L2 (~71 GB/s per CU at the headline shape); the split
+// pack alone is 72 KB per pass against the fp32 pack's 44 KB and measured slower, with half of it resident the layer
+// streams 36 KB (profiles/gcn_split_ab.txt).
+constexpr int GCN_LDS = 3;
+constexpr int GCN_LDS_FRAGS = GCN_LDS * 12;   // 1 KB each: 4 output tiles x hi / mid / lo per pair step
+// the k-th pair step executed: streamed steps (gl .. ns - 1) and resident ones (0 .. gl - 1) alternate,
+// a streamed one first, so a streamed step's refills have two steps to arrive
+constexpr int gcn_step(int k, int gl, int ns) {
+    const int nstr = ns - gl, m = nstr < gl ? nstr : gl;
+    if (k < 2 * m) return (k & 1) ? k / 2 : gl + k / 2;
+    return nstr > gl ? gl + k - m : k - m;
+}
 
 template <int NTO, int NQ, int NQL, int BASE>
 __device__ __forceinline__ void cgemm(__amdgpu_buffer_rsrc_t wr, const floatx4 (&x)[NQ], floatx4 (&o)[NTO]) {
@@ -1019,7 +1036,8 @@ template <int NQE, int NTD, bool SEF, int Q0, bool ZN, class Extra>
 __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs,
                                                 const PosIn &pi, const float (&ef)[EQ_MAX][4],
                                                 float4 (&et)[ETAB_N(Q0)], Extra &&extra, int p, floatx4 (&H)[8],
-                                                float4 (&pre)[PFP], const NextFr &nx, unsigned long long (&T)[10]) {
+                                                float4 (&pre)[PFP], const NextFr &nx, unsigned long long (&T)[10],
+                                                const float4 *gl) {
     constexpr bool ETAB = Q0 > 0;
     static_assert(!(ETAB && SEF), "table mode replaces the streamed edge features");
     using C = WalkConsts<NQE, NTD>;
@@ -1045,6 +1063,19 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         for (int t = 0; t < NTD; ++t) L[t] = ldsx4(bias, t);
     }
     TM_STAMP(1);
+    // ZN: event_gcn's first layer runs on bf16 MFMA too, off the split pack EncW::g13 (pair steps of two input
+    // tiles).  Its first GL pair steps are resident in LDS (gl); the others are streamed in ring order K-outer like
+    // lin_event's: streamed fragment i = (pair step GL + i / 12, output tile (i / 3) % 4, part i % 3).  The ring has
+    // lin_event's depth, so lin_event's ring hands over its 12 slots holding the whole first streamed pair step
+    // (tiles 0..3 x hi / mid / lo) in gb; `pre` carries nothing into event_gcn then (in the two-branch instances it
+    // carries G1's K step 0, tiles 0..3).  The pack's offset off wr rides in the lane offset and the fragment
+    // offsets on an opaque zero, as for ev3 below.
+    constexpr int NSG = (NTD + 1) / 2, GD = 12, GL = GCN_LDS;
+    static_assert(GL >= 1 && GL < NSG, "event_gcn's resident steps");
+    const int vog = lane_id() * 16 + 16 * (int)(P.g13 - P.kv.w);
+    auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
+    float4 gb[ZN ? GD : 1];
+    (void)vog, (void)goff, (void)gb;
     constexpr int JN = 3;                                // node tiles in flight in event_gcn's K loop
     float4 rs[JN], rt[JN];
     auto nload = [&](int q) {
@@ -1056,12 +1087,13 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         constexpr int NS = C::NS, S0 = Q0 / 2;           // 32-wide K steps; table mode starts at step de / 32
         constexpr int N = NTD * (NS - S0) * 3, D = 12;   // fragments (tile, step, part); ring depth: 4 (tile, step)s
         static_assert(D >= PFP && D <= N && D % 3 == 0, "lin_event ring depth");
+        static_assert(D == GD, "the zero-node event_gcn takes over lin_event's ring slots");
         const int vo = lane_id() * 16;
         // the split pack's byte offset off wr in the lane offset, so every fragment offset stays a constant
         const int vo3 = vo + 16 * (int)(P.ev3 - P.kv.w);
         // ring order K-outer: fragment i = (step S0 + i / (3 NTD), tile (i / 3) % NTD, part i % 3).  The first PFP
         // come in pre, requested during the previous pass; the ring's last refills request event_gcn's first K
-        // step (G1 tiles 0..3)
+        // step (G1 tiles 0..3; ZN: all D slots take the g13 pack's first streamed pair step)
         auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
         auto g1f = [](int k) { return LY::G1 / 4 + k * NTD * 64; };
         // the constant rides on an opaque scalar zero defined inside the pass loop: the ~200 distinct offsets are
@@ -1072,6 +1104,10 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         auto wload3 = [&](int i) {
             return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i) * 16, 0));
         };
+        auto wloadg = [&](int i) {
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, z3 + goff(i) * 16, 0));
+        };
+        (void)wloadg, (void)g1f;
         float4 buf[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload3(i);
@@ -1130,6 +1166,7 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
                 auto take = [&](int i) {
                     const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
                     if (i + D < N) buf[i % D] = wload3(i + D);
+                    else if constexpr (ZN) buf[i % D] = wloadg(i + D - N);
                     else if (i + D - N < PFP) buf[i % D] = wload(wr, vo, g1f(i + D - N));
                     return v;
                 };
@@ -1177,12 +1214,21 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         }
         // G1's first fragments: in the ring's slots after a full K loop; the slot pass (K loop cut at qt)
         // requests them now
-        if (p == 2) {
+        if constexpr (ZN) {
+            if (p == 2) {
 #pragma unroll
-            for (int k = 0; k < PFP; ++k) buf[(N + k) % D] = wload(wr, vo, g1f(k));
+                for (int k = 0; k < D; ++k) buf[(N + k) % D] = wloadg(k);
+            }
+#pragma unroll
+            for (int k = 0; k < D; ++k) gb[k] = buf[(N + k) % D];
+        } else {
+            if (p == 2) {
+#pragma unroll
+                for (int k = 0; k < PFP; ++k) buf[(N + k) % D] = wload(wr, vo, g1f(k));
+            }
+#pragma unroll
+            for (int k = 0; k < PFP; ++k) pre[k] = buf[(N + k) % D];
         }
-#pragma unroll
-        for (int k = 0; k < PFP; ++k) pre[k] = buf[(N + k) % D];
     }
     TM_STAMP(2);
     // event_gcn's first layer K-outer: K step q of A = x_s + relu(x_t + L), B = x_t + relu(x_s + L) (:93-96,
@@ -1199,42 +1245,88 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         if constexpr (!ZN) Ht[t] = ldsx4(cs + C::G1C, t);
     }
     if constexpr (ZN) {
-        // one branch: 16 MFMAs per K step, too few to hide a weight fragment requested one step ahead (stamps:
-        // the phase ran at 69 % of the shared-pipe ideal), so the fragments come through a 3-deep ring, two
-        // steps ahead; the next phase's first fragments are requested at step NTD - 2
-        const int vo = lane_id() * 16;
-        float4 wz[3][4];
+        // one branch, on v_mfma_f32_16x16x32_bf16: pair step u multiplies the input tiles 2u and 2u + 1 at once.  The
+        // D tiles of lin_event already have the B operand's lane order -- lane (g, column) holds rows 4g + 0..3 of
+        // each tile -- so K slot j of step u is the activation of L[2u + (j >> 2)][j & 3] (feature gcn_split_col),
+        // the fp32 value the f32 form multiplied, split in registers as lin_event's features are (split_put); the
+        // second half of the last step of an odd tile count is literal zero.  Six products per (tile, step) in
+        // lin_event's order into the fp32 accumulator (which starts from the bias), tile pairs interleaved.  The
+        // steps run in gcn_step's order (one fixed order in every form); a pair's six fragments are fetched -- from
+        // LDS or out of the ring -- while the pair before it multiplies, and the next step's activations are split
+        // between this step's MFMAs.  The ring's last refills request the next phase's first PFP fragments (nx).
+        constexpr int N = (NSG - GL) * 12, D = GD;
+        static_assert(N % D == 0 && D >= PFP, "event_gcn ring depth");
+        const int vo = lane_id() * 16, ln = lane_id();
+        int zg = 0;
+        asm volatile("" : "+s"(zg));
+        auto wloadg = [&](int i) {
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, zg + goff(i) * 16, 0));
+        };
+        auto take = [&](int i) {
+            const float4 v = gb[i % D];
+            if (i + D < N) gb[i % D] = wloadg(i + D);
+            else if (i + D - N < PFP) gb[i % D] = wload(wr, vo, nx.o[i + D - N]);
+            return v;
+        };
+        // the six fragments (tile t: hi, mid, lo; tile t + 1: hi, mid, lo) of pair p = (executed step p / 2, t = 2 (p & 1))
+        auto fetch = [&](int p, float4 (&w)[6]) {
+            const int u = gcn_step(p / 2, GL, NSG), t = 2 * (p & 1);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            wz[0][t] = pre[t];
-            wz[1][t] = wload(wr, vo, LY::G1 / 4 + (t * NTD + 1) * 64);
-        }
-#pragma unroll
-        for (int q = 0; q < NTD; ++q) {
-            if (q + 2 < NTD) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) wz[(q + 2) % 3][t] = wload(wr, vo, LY::G1 / 4 + (t * NTD + q + 2) * 64);
-            } else if (q + 2 == NTD) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) wz[(q + 2) % 3][t] = wload(wr, vo, nx.o[t]);
+            for (int k = 0; k < 6; ++k) {
+                if (u < GL) w[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
+                else w[k] = take(((u - GL) * 4 + t) * 3 + k);
             }
-            extra(q);                                    // the caller's loads placed at step q
-            floatx4 A;
+        };
+        auto act = [&](Split3 &x, int u, int j) {
+            const int q = 2 * u + (j >> 2);
+            if (q < NTD) {
+                split_put(x, j, 0.f + relu(0.f + L[q < NTD ? q : 0][j & 3]));
+            } else {
+                x.h[j] = (__bf16)0.f;
+                x.m[j] = (__bf16)0.f;
+                x.l[j] = (__bf16)0.f;
+            }
+        };
+        Split3 xb;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) A[r] = 0.f + relu(0.f + L[q][r]);
-            // the 4 tiles' chains interleaved; each tile accumulates its k values in the same order as below
+        for (int j = 0; j < 8; ++j) act(xb, gcn_step(0, GL, NSG), j);
+        float4 wb[2][6];
+        fetch(0, wb[0]);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) Hs[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].x, A.x, Hs[t], 0, 0, 0);
+        for (int k = 0; k < NSG; ++k) {
+            extra(2 * k);                                // the caller's loads placed at input tile q
+            if (2 * k + 1 < NTD) extra(2 * k + 1);
+            Split3 xn = xb;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) Hs[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].y, A.y, Hs[t], 0, 0, 0);
+            for (int t = 0; t < 4; t += 2) {
+                const int pp = 2 * k + t / 2;
+                if (pp + 1 < 2 * NSG) fetch(pp + 1, wb[(pp + 1) & 1]);
+                const float4(&w)[6] = wb[pp & 1];
+                const bf16x8 h0 = __builtin_bit_cast(bf16x8, w[0]), m0 = __builtin_bit_cast(bf16x8, w[1]),
+                             l0 = __builtin_bit_cast(bf16x8, w[2]), h1 = __builtin_bit_cast(bf16x8, w[3]),
+                             m1 = __builtin_bit_cast(bf16x8, w[4]), l1 = __builtin_bit_cast(bf16x8, w[5]);
+                Hs[t] = TM_MF32(l0, xb.h, Hs[t]);
+                Hs[t + 1] = TM_MF32(l1, xb.h, Hs[t + 1]);
+                Hs[t] = TM_MF32(h0, xb.l, Hs[t]);
+                Hs[t + 1] = TM_MF32(h1, xb.l, Hs[t + 1]);
+                Hs[t] = TM_MF32(m0, xb.m, Hs[t]);
+                Hs[t + 1] = TM_MF32(m1, xb.m, Hs[t + 1]);
+                Hs[t] = TM_MF32(m0, xb.h, Hs[t]);
+                Hs[t + 1] = TM_MF32(m1, xb.h, Hs[t + 1]);
+                Hs[t] = TM_MF32(h0, xb.m, Hs[t]);
+                Hs[t + 1] = TM_MF32(h1, xb.m, Hs[t + 1]);
+                Hs[t] = TM_MF32(h0, xb.h, Hs[t]);
+                Hs[t + 1] = TM_MF32(h1, xb.h, Hs[t + 1]);
+                if (k + 1 < NSG) {
 #pragma unroll
-            for (int t = 0; t < 4; ++t) Hs[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].z, A.z, Hs[t], 0, 0, 0);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) Hs[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wz[q % 3][t].w, A.w, Hs[t], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 2 * t; j < 2 * t + 4; ++j) act(xn, gcn_step(k + 1, GL, NSG), j);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            xb = xn;
         }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) pre[t] = wz[NTD % 3][t];
+        for (int k = 0; k < PFP; ++k) pre[k] = gb[(N + k) % D];
     } else {
         const int vo = lane_id() * 16;
         float4 wq[2][4];
@@ -1309,8 +1401,9 @@ struct HeadIn {
 };
 
 // per-wave LDS stash of a slot's position-2 results, read by its walks' position-0/1 passes
+template <int NV>         // tiles of V: 8, or 4 in the zero-node form (VZ)
 struct Stash {
-    floatx4 V[8][64];     // kv H_2 + v0 (= G^T Wp): the attention score of position i is V . H_i + cw
+    floatx4 V[NV][64];    // kv H_2 + v0 (= G^T Wp): the attention score of position i is V . H_i + cw
     floatx4 P2[4][64];    // A1D H_2 + cp: attention.MLP.0's input part that does not depend on alpha
     float cw[64];         // u . H_2 + c0 (= Wp . beta)
 };
@@ -1324,7 +1417,7 @@ struct Stash {
 // P2 is the accumulators' initial value.
 template <int NQE, int NTD, bool ZN, int NA>
 __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs, int64_t gw,
-                                          bool valid, const HeadIn &hi, const Stash &st, float s0, float s1,
+                                          bool valid, const HeadIn &hi, const Stash<NA> &st, float s0, float s1,
                                           const floatx4 (&H0)[NA], const floatx4 (&H1)[NA], float4 (&pre)[PFP],
                                           const NextFr &nx_end) {
     static_assert(NA == (ZN ? 4 : 8), "U_i (zero-node form) or H_i");
@@ -1389,7 +1482,7 @@ __device__ __forceinline__ void walk_head(const WalkArgs &a, __amdgpu_buffer_rsr
 // A1G's last refills load nx_end (the next pass's lin_event fragments).
 template <int NQE, int NTD, bool ZN, int NA>
 __device__ __forceinline__ void walk_pool_head(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, bool valid, const HeadIn &hi,
-                                               const Stash &st, float s0, float s1, const floatx4 (&H0)[NA],
+                                               const Stash<NA> &st, float s0, float s1, const floatx4 (&H0)[NA],
                                                const floatx4 (&H1)[NA], float4 (&pre)[PFP], const NextFr &nx_end,
                                                floatx4 (&acc)[4]) {
     static_assert(NA == (ZN ? 4 : 8), "U_i (zero-node form) or H_i");
@@ -1425,7 +1518,7 @@ __device__ __forceinline__ void walk_pool_head(const WalkArgs &a, __amdgpu_buffe
 
 // this column's V . H (the 4 lane groups' parts summed); ZN: VZ . U over the first 4 tiles
 template <bool ZN = false>
-__device__ __forceinline__ float score_dot(const Stash &st, const floatx4 (&H)[8]) {
+__device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const floatx4 (&H)[8]) {
     const int lane = threadIdx.x & 63;
     float s = 0.f;
 #pragma unroll
@@ -1485,8 +1578,8 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     int64_t eg;
     int32_t j;
     coords(unit, valid, eg, j);
-    // LDS: per-wave stash of the slot's position-2 results (12.25 KB per wave), then the constant table
-    __shared__ Stash stash[WALK_WPB];
+    // LDS: per-wave stash of the slot's position-2 results (12.25 KB per wave; ZN 8.25 KB), then the constant table
+    __shared__ Stash<NA> stash[WALK_WPB];
     __shared__ float4 cs4[(C::SIZE + 3) / 4];
     float *cs = reinterpret_cast<float *>(cs4);
 #ifdef TM_TRACE
@@ -1494,6 +1587,16 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     int trn = 0;
     const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
 #endif
+    // ZN: event_gcn's resident weight fragments (the g13 pack's pair steps 0 .. GCN_LDS - 1, in (step, tile, part)
+    // order; see encode_position)
+    __shared__ float4 gl[ZN ? GCN_LDS_FRAGS * 64 : 1];
+    if constexpr (ZN) {
+        constexpr int NSG = (NTD + 1) / 2;
+        for (int i = threadIdx.x; i < GCN_LDS_FRAGS * 64; i += blockDim.x) {
+            const int f = i >> 6, l = i & 63;
+            gl[i] = P.g13[((((f / 3) % 4) * NSG + f / 12) * 3 + f % 3) * 64 + l];
+        }
+    }
     load_consts<NQE, NTD, ZN>(P, cs);
     __syncthreads();
 #ifdef TM_TRACE
@@ -1505,7 +1608,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     }
 #endif
     if (unit >= n_units) return;                        // whole wave idle (wave-uniform)
-    Stash &st = stash[threadIdx.x >> 6];
+    Stash<NA> &st = stash[threadIdx.x >> 6];
     // every weight fragment off one buffer resource (WalkLay offsets from the folded region's base)
     const auto wr = wrsrc(P.kv.w);
     // position 0's hidden vector (U_0 in the zero-node form) and score, carried to the position-1 pass; every
@@ -1602,7 +1705,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
         const NextFr nx_pos = ZN ? pair_first<4>(p == 2 ? FoldLay::A1DZ / 4 : FoldLay::A1GZ / 4)
                                  : pair_first<8>(p == 2 ? FoldLay::A1D / 4 : FoldLay::A1G / 4);
         encode_position<NQE, NTD, SEF, QE0, ZN>(a, wr, cs, cur, ef, et, extra, p, H, pre,
-                                                p == 0 ? lin0 : nx_pos, T);
+                                                p == 0 ? lin0 : nx_pos, T, gl);
         if constexpr (QE0 == 0) load_ef(a, nxt.edge(), ef);
         else load_et<QE0>(a, nxt.edge(), et);
         cur = nxt;
@@ -1737,7 +1840,7 @@ static bool walk_layout_ok(const EncW &P, int nqe) {
     return at(P.ev.w, ev) && at(P.g1.w, g1) && at(P.m2.w, m2) && at(P.a1d.w, FoldLay::A1D) &&
            at(P.a1g.w, FoldLay::A1G) && at(P.m1a2.w, FoldLay::M1A2) && at(P.kvz.w, FoldLay::KVZ) &&
            at(P.a1dz.w, FoldLay::A1DZ) && at(P.a1gz.w, FoldLay::A1GZ) && P.g1.nt == 4 && P.g1.nq == 11 && P.m2.nt == 4 && P.m2.nq == 5 && P.ev.nt == 11 && P.ev.nq == nqe &&
-           P.ev3 && P.ns3 == (nqe + 1) / 2;
+           P.ev3 && P.ns3 == (nqe + 1) / 2 && P.g13 && P.nsg == 6;
 }
 
 // ------------------------------------------------------------------ per-edge dependency gate table
@@ -2078,6 +2181,9 @@ extern "C" int tm_weights_create_ex(int32_t de, int32_t dn, int32_t h, int32_t i
     const int ns3 = (P.kev + 31) / 32;
     total = (total + 63) & ~(size_t)63;
     const size_t ev3 = total; total += (size_t)(r16(dn) / 16) * ns3 * 3 * 256;
+    // event_gcn's first layer likewise (EncW::g13): 3 fragments per (output tile, pair step of two input tiles)
+    const int nsg = (r16(dn) / 16 + 1) / 2;
+    const size_t g13 = total; total += (size_t)(r16(h) / 16) * nsg * 3 * 256;
     int prev = 0;
     (void)hipGetDevice(&prev);
     if (hipSetDevice(device) != hipSuccess || hipMalloc(&w->buf, total * sizeof(float)) != hipSuccess ||
@@ -2104,6 +2210,8 @@ extern "C" int tm_weights_create_ex(int32_t de, int32_t dn, int32_t h, int32_t i
     P.qt = (de + 3 + 31) / 32;
     P.ev3 = reinterpret_cast<const float4 *>(w->buf + ev3);
     P.ns3 = ns3;
+    P.g13 = reinterpret_cast<const float4 *>(w->buf + g13);
+    P.nsg = nsg;
     {   // folded packs (tmk::FoldLay)
         using F = tmk::FoldLay;
         struct FL {
@@ -2153,6 +2261,19 @@ extern "C" uint64_t tm_weights_version(const tm_weights *w) { return w ? w->vers
 
 extern "C" void tm_weight_split3(const float *in, int64_t n, uint16_t *hi, uint16_t *mid, uint16_t *lo) {
     for (int64_t i = 0; i < n; ++i) split3(in[i], hi[i], mid[i], lo[i]);
+}
+
+// the g1 split pack (EncW::g13) of a row-major W[nout][dn] on the host, with the pack launch's own index and
+// split code: out holds (r16(nout) / 16) * ((r16(dn) / 16 + 1) / 2) * 3 fragments of 512 bf16 bit patterns
+extern "C" void tm_weight_gcn_split(const float *w, int32_t nout, int32_t dn, uint16_t *out) {
+    const int nt = tmk::r16(nout) / 16, nsg = (tmk::r16(dn) / 16 + 1) / 2;
+    for (int64_t e = 0; e < (int64_t)nt * nsg * 512; ++e) {
+        const int j = e & 7, l = (e >> 3) & 63;
+        const int64_t ts = e >> 9;
+        const int o = 16 * (int)(ts / nsg) + (l & 15), c = tmk::gcn_split_col((int)(ts % nsg), l >> 4, j);
+        uint16_t *d = out + ts * 3 * 512 + l * 8 + j;
+        split3((o < nout && c < dn) ? w[(int64_t)o * dn + c] : 0.f, d[0], d[512], d[1024]);
+    }
 }
 
 extern "C" int tm_weights_set_node_zero(tm_weights *w, int32_t node_zero) {

@@ -33,6 +33,13 @@ struct EncW {
     // rows >= dn and k >= kev are zero.  In tm_weights::buf, so one buffer resource reaches it.
     const float4 *ev3;
     int ns3;
+    // event_gcn's first layer (g1) for the zero-node walk kernel's bf16 MFMA form, split3 like ev3: per (output
+    // tile t, pair step u, part) one 1 KB fragment at float4 offset ((t * nsg + u) * 3 + part) * 64.  A pair step
+    // spans the input tiles 2u and 2u + 1 in the D-tile lane order lin_event leaves them in: lane l (row
+    // 16t + (l & 15), group g = l >> 4) holds W[row][gcn_split_col(u, g, j)], j = 0..7; zero for a column >= dn
+    // (the padding of the last tile, and with an odd tile count the whole second half of the last step).
+    const float4 *g13;
+    int nsg;   // pair steps: (r16(dn) / 16 + 1) / 2
     // lin_event's folded time steps alone (evc - bias, fp64 sum rounded once): the table-mode slot pass,
     // whose edge-table row already carries the bias
     const float *devc;
@@ -151,6 +158,15 @@ __host__ __device__ inline void split3(float v, uint16_t &hi, uint16_t &mid, uin
     // a zero part takes the value's sign, so that -0 = (-0) + (-0) + (-0) bit for bit
     if ((mid & 0x7fffu) == 0) mid = hi & 0x8000u;
     if ((lo & 0x7fffu) == 0) lo = hi & 0x8000u;
+}
+
+// input feature in K slot (lane group g, element j) of pair step u of the g1 split pack (EncW::g13): elements 0..3
+// from input tile 2u, 4..7 from tile 2u + 1, each lane's 4 rows of the f32 D-tile layout
+__host__ __device__ constexpr int gcn_split_col(int u, int g, int j) { return 16 * (2 * u + (j >> 2)) + 4 * g + (j & 3); }
+// column of element (K step s, lane group g, element j) of a split pack: mode 1 = ev3 (plain 32-wide steps),
+// mode 2 = g13 (pair steps)
+__host__ __device__ constexpr int split_pack_col(int mode, int s, int g, int j) {
+    return mode == 2 ? gcn_split_col(s, g, j) : 32 * s + 8 * g + j;
 }
 
 // The dependency gate's logit d3 . G2 over its h2 = h/2 features in ONE fixed order, shared by the

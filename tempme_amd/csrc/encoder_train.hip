@@ -34,7 +34,9 @@ struct PackJob {
     const float *src;
     float *dst;
     int32_t so, sc, nout, k, nt, nq;
-    int32_t split;   // 1: the three-way bf16 split pack of EncW::ev3 (nq = its 32-wide K steps; dst in bf16 units)
+    // 1: the three-way bf16 split pack of EncW::ev3 (nq = its 32-wide K steps; dst in bf16 units); 2: that of
+    // EncW::g13 (nq = its pair steps, columns permuted by gcn_split_col)
+    int32_t split;
     int64_t begin;
 };
 constexpr int MAX_PACK_JOBS = 56;
@@ -57,7 +59,7 @@ __global__ void pack_jobs_kernel(PackJobs J) {
         if (p.split) {   // element (t, s, lane, j) -> its hi / mid / lo fragments (512 bf16 each)
             const int j = e & 7, l = (e >> 3) & 63;
             const int64_t ts = e >> 9;
-            const int o = 16 * (int)(ts / p.nq) + (l & 15), c = 32 * (int)(ts % p.nq) + 8 * (l >> 4) + j;
+            const int o = 16 * (int)(ts / p.nq) + (l & 15), c = split_pack_col(p.split, (int)(ts % p.nq), l >> 4, j);
             uint16_t hi, mid, lo;
             split3((o < p.nout && c < p.k) ? p.src[(int64_t)o * p.so + (int64_t)c * p.sc] : 0.f, hi, mid, lo);
             uint16_t *d = reinterpret_cast<uint16_t *>(p.dst) + ts * 3 * 512 + l * 8 + j;
@@ -1648,6 +1650,20 @@ void pack_all_weights(tm_weights *w, const float *const *t, hipStream_t s) {
         p.nt = w->P.ev.nt;
         p.nq = w->P.ns3;
         p.split = 1;
+        p.begin = total;
+        total += (int64_t)p.nt * p.nq * 512;
+    }
+    {   // event_gcn's first layer's split pack for the zero-node walk kernel (EncW::g13), from g1's raw tensor
+        PackJob &p = P.j[P.n++];
+        p.src = t[2];
+        p.dst = const_cast<float *>(reinterpret_cast<const float *>(w->P.g13));
+        p.so = dn;
+        p.sc = 1;
+        p.nout = h;
+        p.k = dn;
+        p.nt = w->P.g1.nt;
+        p.nq = w->P.nsg;
+        p.split = 2;
         p.begin = total;
         total += (int64_t)p.nt * p.nq * 512;
     }

@@ -1,0 +1,157 @@
+"""CPU: what test_gpu_edge_width.py rests on.
+
+1. The dispatch arithmetic of the motif encoder, restated: which kernel instance an edge-feature width reaches
+   (dn = 172, hid_dim = 64, if_cat_feature = True).  edge_width_inputs.WIDTHS must match the restatement row by row
+   and must hold a width for every class that some constructible width reaches.
+2. The reference alone is well inside the contract: oracle/encoder_ref.forward in fp32 against fp64 stays within
+   0.1 of atol 1e-6 + rtol 1e-5 at every width.
+3. The inputs can show a wrong column: dropping one edge-feature column or one lin_event weight column moves the
+   fp32 oracle by at least 5 times the contract bound on at least one walk, at every width.
+"""
+import numpy as np
+import pytest
+
+import edge_width_inputs as EW
+
+G, B, M = EW.SMALL + (3,)
+EQ_MAX = 4
+
+
+def r16(x):
+    return (x + 15) // 16 * 16
+
+
+def dispatch(de, dn=EW.DN):
+    """The instance an edge-feature width reaches, restated from tempme_amd/csrc:
+
+    * encoder.hip, encoder_fwd_impl: nqe = r16(kev) / 16, ntd = r16(dn) / 16; narrow = 11 <= nqe <= 14 and
+      de <= 16 * EQ_MAX; wide = nqe in (21, 22) and de > 16 * EQ_MAX and de % 4 == 0; the fused walk_kernel<nqe>
+      runs when ntd == 11, dn % 4 == 0 and (narrow or wide) (h = 64 with the category one-hot, as here), else
+      gcn_kernel + head_kernel.  launch_walk_pool takes the same instance table.
+    * encoder.hip, etab_q0: q0 = de / 16; a per-edge-id table for q0 == 2 with 11 <= nqe <= 14 and d1.nq == 13, or
+      q0 == 10 with nqe in (21, 22) and d1.nq == 22 (d1.nq = r16(kdep) / 16, kdep = de + dn).
+    * encoder.hip, load_ef (plain mode, narrow): the 32-wide step s is one float4 per half when de % 4 == 0 and
+      32 s + 32 <= de, zero when 32 s >= de, else scalar loads clamped to the row; wide widths stream their row
+      (ef_step).
+    * encoder.hip, launch_edge_tables: with a table gate_reg_kernel<13, 3, nqe> (q0 == 2) or <22, 11, nqe>; without
+      one gate_reg_kernel<d1.nq> for d1.nq in (11, 12, 13, 22), else the LDS gate_table_kernel.
+    * encoder_train.hip, gcn_bwd_uses_reg / launch_gcn_fwd_reg: the register-resident event_gcn kernels at Q = nqe
+      when r16(dn) == 176, dn % 4 == 0, de % 4 == 0 and 11 <= nqe <= 14, else the LDS-tiled ones.
+    """
+    kev, kdep = de + 3 + dn, de + dn
+    nqe, d1nq, ntd, q0 = r16(kev) // 16, r16(kdep) // 16, r16(dn) // 16, de // 16
+    narrow = 11 <= nqe <= 14 and de <= 16 * EQ_MAX
+    wide = nqe in (21, 22) and de > 16 * EQ_MAX and de % 4 == 0
+    fused = ntd == 11 and dn % 4 == 0 and (narrow or wide)
+    tq = 0
+    if ntd == 11 and dn % 4 == 0:
+        if q0 == 2 and 11 <= nqe <= 14 and d1nq == 13:
+            tq = 2
+        elif q0 == 10 and nqe in (21, 22) and d1nq == 22:
+            tq = 10
+    if not fused:
+        load = "none"
+    elif wide:
+        load = "streamed"
+    else:
+        steps = []
+        for s in (0, 1):
+            if de % 4 == 0 and 32 * s + 32 <= de:
+                steps.append("float4")
+            elif 32 * s < de:
+                steps.append("scalar")
+        load = "+".join(steps)
+    if tq:
+        gate = "reg<%d,%d,%d>" % ((13, 3, nqe) if tq == 2 else (22, 11, nqe))
+    elif d1nq in (11, 12, 13, 22):
+        gate = "reg<%d>" % d1nq
+    else:
+        gate = "lds"
+    reg = r16(dn) == 176 and dn % 4 == 0 and de % 4 == 0 and 11 <= nqe <= 14
+    return dict(de=de, nqe=nqe, d1nq=d1nq, table=tq > 0, fused=fused, load_ef=load, gate=gate,
+                train="reg%d" % nqe if reg else "lds")
+
+
+def classes(row):
+    """The classes of one width, one per axis of the issue's table."""
+    table = "none" if not (row["table"] and row["fused"]) else "aligned" if row["de"] % 4 == 0 else "unaligned"
+    return {("walk", row["nqe"] if row["fused"] else "unfused"), ("table", table), ("load_ef", row["load_ef"]),
+            ("gate", row["gate"]), ("train", row["train"])}
+
+
+def test_widths_match_the_dispatch_arithmetic():
+    for de, row in EW.WIDTHS.items():
+        assert dispatch(de) == row, de
+    # the hand-worked rows of the issue, as they were stated there
+    assert dispatch(17)["nqe"] == 12 and 17 + 3 + 172 == 192
+    assert dispatch(33)["nqe"] == 13 and 33 + 3 + 172 == 208 and dispatch(33)["table"]
+    assert dispatch(36)["d1nq"] == 13 and 36 + 172 == 208
+    assert dispatch(49)["nqe"] == 14 and 49 + 3 + 172 == 224
+    assert not dispatch(50)["fused"] and not dispatch(37)["table"] and not dispatch(48)["table"]
+    assert not dispatch(160)["table"] and not dispatch(176)["table"]
+
+
+def test_widths_cover_every_reachable_class():
+    reachable = set()
+    for de in range(1, 400):
+        reachable |= classes(dispatch(de))
+    covered = set()
+    for row in EW.WIDTHS.values():
+        covered |= classes(row)
+    assert reachable - covered == set(), sorted(map(str, reachable - covered))
+    want = {("walk", q) for q in (11, 12, 13, 14, 21, 22, "unfused")}
+    want |= {("table", t) for t in ("aligned", "unaligned", "none")}
+    want |= {("load_ef", k) for k in ("scalar", "float4", "scalar+scalar", "float4+scalar", "streamed")}
+    want |= {("gate", k) for k in ("reg<11>", "reg<12>", "reg<13>", "reg<22>", "reg<13,3,13>", "reg<13,3,14>",
+                                   "reg<22,11,22>", "lds")}
+    want |= {("train", k) for k in ("reg12", "reg13", "reg14", "lds")}
+    assert want <= covered, sorted(map(str, want - covered))
+    # the instances the dispatch code names that no width reaches at dn = 172 (DESIGN records them)
+    for de in range(1, 400):
+        d = dispatch(de)
+        assert not (d["table"] and de // 16 == 2 and d["nqe"] in (11, 12)), de       # launch_walk<11|12, ., 2>
+        assert not (d["table"] and d["nqe"] == 21), de                                # launch_walk<21, ., 10>
+        assert d["train"] != "reg11", de                                              # gcn_*_reg_kernel<11>
+
+
+@pytest.mark.parametrize("node_feat", ["uniform", "zeros"])
+@pytest.mark.parametrize("de", list(EW.WIDTHS))
+def test_reference_alone_is_inside_the_contract(de, node_feat):
+    _, sd, nf, ef = EW.model(de, node_feat)
+    r32 = EW.oracle32(de, node_feat, G, B, M).astype(np.float64)
+    r64 = EW.oracle(sd, nf, ef, G, B, M, double=True)
+    assert r64.dtype == np.float64
+    ratio = (np.abs(r32 - r64) / EW.bound(r64)).max()
+    print("de %d %s: fp32 oracle vs fp64, worst diff / bound %.3g" % (de, node_feat, ratio))
+    assert ratio <= 0.1
+
+
+def _drops(de):
+    """name -> (edge-feature column to zero or None, lin_event weight column to zero or None)"""
+    return {"e_feat[:, de - 1]": (de - 1, None), "e_feat[:, 4 ((de - 1) // 4)]": (4 * ((de - 1) // 4), None),
+            "e_feat[:, 0]": (0, None), "lin_event.weight[:, de + 2]": (None, de + 2),
+            "lin_event.weight[:, de + 3 + 171]": (None, de + 3 + 171)}
+
+
+@pytest.mark.parametrize("node_feat", ["uniform", "zeros"])
+@pytest.mark.parametrize("de", list(EW.WIDTHS))
+def test_inputs_can_show_a_wrong_column(de, node_feat):
+    """A kernel that dropped (or misplaced) the last edge-feature column, the first column of the last float4, column
+    0, the third count or the last time feature would move the output by at least 5 bounds on some walk."""
+    _, sd, nf, ef = EW.model(de, node_feat)
+    ref = EW.oracle32(de, node_feat, G, B, M)
+    assert sd["event_conv.lin_event.weight"].shape[1] == de + 3 + 172
+    worst = {}
+    for name, (ecol, wcol) in _drops(de).items():
+        sd2, ef2 = dict(sd), ef
+        if ecol is not None:
+            ef2 = ef.clone()
+            ef2[:, ecol] = 0
+        else:
+            w = sd["event_conv.lin_event.weight"].clone()
+            w[:, wcol] = 0
+            sd2["event_conv.lin_event.weight"] = w
+        out = EW.oracle(sd2, nf, ef2, G, B, M)
+        worst[name] = float((np.abs(out - ref) / EW.bound(ref)).max())
+    print("de %d %s: " % (de, node_feat) + ", ".join("%s %.3g" % kv for kv in worst.items()))
+    assert min(worst.values()) >= 5.0, worst

@@ -89,6 +89,9 @@ VARIANTS = {
     "hid128": dict(hid_dim=128),
     "hid48_padded": dict(hid_dim=48),
     "de1": dict(de=1),                                               # the LDS-tiled event_gcn kernels
+    "de4": dict(de=4),                                               # register-resident event_gcn, Q = 12
+    "de36": dict(de=36),                                             # register-resident event_gcn, Q = 14
+    "de36_zero_nodes": dict(de=36, zero_nodes=True),
 }
 
 

@@ -58,12 +58,15 @@ int tm_version(void);
 /* Test / diagnostic options, process-wide, all 0 (off) in the product path -- the library reads no environment
  * variables.  TM_DEBUG_FORCE_UNKEYED: the samplers' two-compare rank kernels on any graph (tests compare them with
  * the keyed one-compare kernels); TM_DEBUG_HOST_BUILD: tm_graph_build_edges on the host builder (tests compare it
- * with the device builder); TM_DEBUG_GRAPH_TIMING: the graph build's phase times on stderr. */
+ * with the device builder); TM_DEBUG_GRAPH_TIMING: the graph build's phase times on stderr; TM_DEBUG_WALK_SINGLE: the
+ * encoder's zero-node table-mode walk kernel with one walk position per pass instead of the pair pass (tests compare
+ * the two bit for bit). */
 #define TM_DEBUG_FORCE_UNKEYED 1
 #define TM_DEBUG_HOST_BUILD 2
 #define TM_DEBUG_GRAPH_TIMING 3
 #define TM_DEBUG_WALK_BLOCKS 4   /* > 0: cap the persistent walk kernel's grid at this many workgroups (A/B tools) */
-#define TM_DEBUG_N_OPTS 5
+#define TM_DEBUG_WALK_SINGLE 5   /* != 0: the zero-node table-mode walk kernel encodes one position per pass (tests, A/B) */
+#define TM_DEBUG_N_OPTS 6
 int tm_debug_set(int32_t opt, int32_t value);
 /* Threads of the host-side graph builder (0 = the CPUs this process may run on, at most 64). */
 int tm_set_host_threads(int32_t n);

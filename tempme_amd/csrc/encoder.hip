@@ -655,6 +655,9 @@ constexpr int WALK_WPB = 4;
 // streams 36 KB (profiles/gcn_split_ab.txt).
 constexpr int GCN_LDS = 3;
 constexpr int GCN_LDS_FRAGS = GCN_LDS * 12;   // 1 KB each: 4 output tiles x hi / mid / lo per pair step
+// weight-fragment ring depths of the pair pass (encode_pair): two accumulator sets leave the rings fewer registers,
+// and a lin_event fragment covers twice the MFMA time there
+constexpr int PAIR_LIN_RING = 6, PAIR_GCN_RING = 6;
 // the k-th pair step executed: streamed steps (gl .. ns - 1) and resident ones (0 .. gl - 1) alternate,
 // a streamed one first, so a streamed step's refills have two steps to arrive
 constexpr int gcn_step(int k, int gl, int ns) {
@@ -874,9 +877,9 @@ struct WalkArgs {
 };
 
 // Phase timing (debug builds only, -DTM_STAMPS; tools/stamps.py): s_memtime deltas of lane 0 per
-// pass type accumulated for every 16th workgroup (sampled over the whole launch).
+// pass type (a pair pass: encode_pair's phases) accumulated for every 16th workgroup (sampled over the whole launch).
 #ifdef TM_STAMPS
-__device__ unsigned long long g_st[3][10];
+__device__ unsigned long long g_st[4][10];   // pass types 0, 1 (a position), 2 (slot), 3 (pair)
 __device__ unsigned long long g_live;   // waves inside the pass loop right now
 #define TM_STAMP(k)                                 \
     do {                                            \
@@ -889,7 +892,8 @@ __device__ unsigned long long g_live;   // waves inside the pass loop right now
 #endif
 // Wave timeline (debug builds only, -DTM_TRACE; tools/walk_trace.py): per wave of the last launch, s_memrealtime
 // (100 MHz) at [0] entry, [1] after the constant table, [2..15] the end of each pass of its first two units,
-// [16..27] the end of each of its first 12 units, [28] its unit count, [29] HW_ID | XCC_ID << 32
+// [16..27] the end of each of its first 12 units, [28] its unit count, [29] HW_ID | XCC_ID << 32, [30] passes per
+// unit (7 slots per unit in [2..15]: 1 + 2M single-position passes, 1 + M with the pair pass)
 #ifdef TM_TRACE
 __device__ unsigned long long g_tr[8192][32];
 #endif
@@ -1017,6 +1021,101 @@ __device__ __forceinline__ void load_et(const WalkArgs &a, int32_t e, float4 (&e
         const int g = lane_id() >> 4;
 #pragma unroll
         for (int t = 0; t < 11; ++t) et[t] = trow[4 * t + g];
+    }
+}
+
+// event_gcn's first layer of the zero-node instances for one column set: Hs (on entry the bias) += g1 relu(L), on
+// v_mfma_f32_16x16x32_bf16 off the split pack EncW::g13.  Pair step u multiplies the input tiles 2u and 2u + 1 at
+// once.  The D tiles of lin_event already have the B operand's lane order -- lane (g, column) holds rows 4g + 0..3 of
+// each tile -- so K slot j of step u is the activation of L[2u + (j >> 2)][j & 3] (feature gcn_split_col), the fp32
+// value the f32 form multiplied, split in registers as lin_event's features are (split_put); the second half of the
+// last step of an odd tile count is literal zero.  Six products per (tile, step) in lin_event's order into the fp32
+// accumulator, tile pairs interleaved.  The steps run in gcn_step's order (one fixed order in every form); a pair's
+// six fragments are fetched -- from LDS (gl) or out of the ring gb, which holds the first streamed pair step on
+// entry (vog: the pack's lane offset off wr) -- while the pair before it multiplies, and the next step's
+// activations are split between this step's MFMAs.  The ring's last refills request the next phase's first PFP
+// fragments (nx, returned in pre) or, AGAIN (the pair pass: the other column set's layer follows), the pack's first
+// streamed pair step once more, left in gb.  D: the ring's depth (the ring holds fragments 0 .. D - 1 on entry).
+template <int NTD, bool AGAIN, int D, class Extra>
+__device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const float4 *gl, const floatx4 (&L)[NTD],
+                                       float4 (&gb)[D], Extra &&extra, floatx4 (&Hs)[4], float4 (&pre)[PFP],
+                                       const NextFr &nx) {
+    constexpr int NSG = (NTD + 1) / 2, GL = GCN_LDS, N = (NSG - GL) * 12;
+    static_assert(N % D == 0 && D >= PFP, "event_gcn ring depth");
+    const int vo = lane_id() * 16, ln = lane_id();
+    auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
+    int zg = 0;
+    asm volatile("" : "+s"(zg));
+    auto wloadg = [&](int i) {
+        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, zg + goff(i) * 16, 0));
+    };
+    auto take = [&](int i) {
+        const float4 v = gb[i % D];
+        if (i + D < N) gb[i % D] = wloadg(i + D);
+        else if constexpr (AGAIN) gb[i % D] = wloadg(i + D - N);
+        else if (i + D - N < PFP) gb[i % D] = wload(wr, vo, nx.o[i + D - N]);
+        return v;
+    };
+    // the six fragments (tile t: hi, mid, lo; tile t + 1: hi, mid, lo) of pair p = (executed step p / 2, t = 2 (p & 1))
+    auto fetch = [&](int p, float4 (&w)[6]) {
+        const int u = gcn_step(p / 2, GL, NSG), t = 2 * (p & 1);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            if (u < GL) w[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
+            else w[k] = take(((u - GL) * 4 + t) * 3 + k);
+        }
+    };
+    auto act = [&](Split3 &x, int u, int j) {
+        const int q = 2 * u + (j >> 2);
+        if (q < NTD) {
+            split_put(x, j, 0.f + relu(0.f + L[q < NTD ? q : 0][j & 3]));
+        } else {
+            x.h[j] = (__bf16)0.f;
+            x.m[j] = (__bf16)0.f;
+            x.l[j] = (__bf16)0.f;
+        }
+    };
+    Split3 xb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) act(xb, gcn_step(0, GL, NSG), j);
+    float4 wb[2][6];
+    fetch(0, wb[0]);
+#pragma unroll
+    for (int k = 0; k < NSG; ++k) {
+        extra(2 * k);                                // the caller's loads placed at input tile q
+        if (2 * k + 1 < NTD) extra(2 * k + 1);
+        Split3 xn = xb;
+#pragma unroll
+        for (int t = 0; t < 4; t += 2) {
+            const int pp = 2 * k + t / 2;
+            if (pp + 1 < 2 * NSG) fetch(pp + 1, wb[(pp + 1) & 1]);
+            const float4(&w)[6] = wb[pp & 1];
+            const bf16x8 h0 = __builtin_bit_cast(bf16x8, w[0]), m0 = __builtin_bit_cast(bf16x8, w[1]),
+                         l0 = __builtin_bit_cast(bf16x8, w[2]), h1 = __builtin_bit_cast(bf16x8, w[3]),
+                         m1 = __builtin_bit_cast(bf16x8, w[4]), l1 = __builtin_bit_cast(bf16x8, w[5]);
+            Hs[t] = TM_MF32(l0, xb.h, Hs[t]);
+            Hs[t + 1] = TM_MF32(l1, xb.h, Hs[t + 1]);
+            Hs[t] = TM_MF32(h0, xb.l, Hs[t]);
+            Hs[t + 1] = TM_MF32(h1, xb.l, Hs[t + 1]);
+            Hs[t] = TM_MF32(m0, xb.m, Hs[t]);
+            Hs[t + 1] = TM_MF32(m1, xb.m, Hs[t + 1]);
+            Hs[t] = TM_MF32(m0, xb.h, Hs[t]);
+            Hs[t + 1] = TM_MF32(m1, xb.h, Hs[t + 1]);
+            Hs[t] = TM_MF32(h0, xb.m, Hs[t]);
+            Hs[t + 1] = TM_MF32(h1, xb.m, Hs[t + 1]);
+            Hs[t] = TM_MF32(h0, xb.h, Hs[t]);
+            Hs[t + 1] = TM_MF32(h1, xb.h, Hs[t + 1]);
+            if (k + 1 < NSG) {
+#pragma unroll
+                for (int j = 2 * t; j < 2 * t + 4; ++j) act(xn, gcn_step(k + 1, GL, NSG), j);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        xb = xn;
+    }
+    if constexpr (!AGAIN) {
+#pragma unroll
+        for (int k = 0; k < PFP; ++k) pre[k] = gb[(N + k) % D];
     }
 }
 
@@ -1245,88 +1344,8 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         if constexpr (!ZN) Ht[t] = ldsx4(cs + C::G1C, t);
     }
     if constexpr (ZN) {
-        // one branch, on v_mfma_f32_16x16x32_bf16: pair step u multiplies the input tiles 2u and 2u + 1 at once.  The
-        // D tiles of lin_event already have the B operand's lane order -- lane (g, column) holds rows 4g + 0..3 of
-        // each tile -- so K slot j of step u is the activation of L[2u + (j >> 2)][j & 3] (feature gcn_split_col),
-        // the fp32 value the f32 form multiplied, split in registers as lin_event's features are (split_put); the
-        // second half of the last step of an odd tile count is literal zero.  Six products per (tile, step) in
-        // lin_event's order into the fp32 accumulator (which starts from the bias), tile pairs interleaved.  The
-        // steps run in gcn_step's order (one fixed order in every form); a pair's six fragments are fetched -- from
-        // LDS or out of the ring -- while the pair before it multiplies, and the next step's activations are split
-        // between this step's MFMAs.  The ring's last refills request the next phase's first PFP fragments (nx).
-        constexpr int N = (NSG - GL) * 12, D = GD;
-        static_assert(N % D == 0 && D >= PFP, "event_gcn ring depth");
-        const int vo = lane_id() * 16, ln = lane_id();
-        int zg = 0;
-        asm volatile("" : "+s"(zg));
-        auto wloadg = [&](int i) {
-            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, zg + goff(i) * 16, 0));
-        };
-        auto take = [&](int i) {
-            const float4 v = gb[i % D];
-            if (i + D < N) gb[i % D] = wloadg(i + D);
-            else if (i + D - N < PFP) gb[i % D] = wload(wr, vo, nx.o[i + D - N]);
-            return v;
-        };
-        // the six fragments (tile t: hi, mid, lo; tile t + 1: hi, mid, lo) of pair p = (executed step p / 2, t = 2 (p & 1))
-        auto fetch = [&](int p, float4 (&w)[6]) {
-            const int u = gcn_step(p / 2, GL, NSG), t = 2 * (p & 1);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                if (u < GL) w[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
-                else w[k] = take(((u - GL) * 4 + t) * 3 + k);
-            }
-        };
-        auto act = [&](Split3 &x, int u, int j) {
-            const int q = 2 * u + (j >> 2);
-            if (q < NTD) {
-                split_put(x, j, 0.f + relu(0.f + L[q < NTD ? q : 0][j & 3]));
-            } else {
-                x.h[j] = (__bf16)0.f;
-                x.m[j] = (__bf16)0.f;
-                x.l[j] = (__bf16)0.f;
-            }
-        };
-        Split3 xb;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) act(xb, gcn_step(0, GL, NSG), j);
-        float4 wb[2][6];
-        fetch(0, wb[0]);
-#pragma unroll
-        for (int k = 0; k < NSG; ++k) {
-            extra(2 * k);                                // the caller's loads placed at input tile q
-            if (2 * k + 1 < NTD) extra(2 * k + 1);
-            Split3 xn = xb;
-#pragma unroll
-            for (int t = 0; t < 4; t += 2) {
-                const int pp = 2 * k + t / 2;
-                if (pp + 1 < 2 * NSG) fetch(pp + 1, wb[(pp + 1) & 1]);
-                const float4(&w)[6] = wb[pp & 1];
-                const bf16x8 h0 = __builtin_bit_cast(bf16x8, w[0]), m0 = __builtin_bit_cast(bf16x8, w[1]),
-                             l0 = __builtin_bit_cast(bf16x8, w[2]), h1 = __builtin_bit_cast(bf16x8, w[3]),
-                             m1 = __builtin_bit_cast(bf16x8, w[4]), l1 = __builtin_bit_cast(bf16x8, w[5]);
-                Hs[t] = TM_MF32(l0, xb.h, Hs[t]);
-                Hs[t + 1] = TM_MF32(l1, xb.h, Hs[t + 1]);
-                Hs[t] = TM_MF32(h0, xb.l, Hs[t]);
-                Hs[t + 1] = TM_MF32(h1, xb.l, Hs[t + 1]);
-                Hs[t] = TM_MF32(m0, xb.m, Hs[t]);
-                Hs[t + 1] = TM_MF32(m1, xb.m, Hs[t + 1]);
-                Hs[t] = TM_MF32(m0, xb.h, Hs[t]);
-                Hs[t + 1] = TM_MF32(m1, xb.h, Hs[t + 1]);
-                Hs[t] = TM_MF32(h0, xb.m, Hs[t]);
-                Hs[t + 1] = TM_MF32(h1, xb.m, Hs[t + 1]);
-                Hs[t] = TM_MF32(h0, xb.h, Hs[t]);
-                Hs[t + 1] = TM_MF32(h1, xb.h, Hs[t + 1]);
-                if (k + 1 < NSG) {
-#pragma unroll
-                    for (int j = 2 * t; j < 2 * t + 4; ++j) act(xn, gcn_step(k + 1, GL, NSG), j);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            xb = xn;
-        }
-#pragma unroll
-        for (int k = 0; k < PFP; ++k) pre[k] = gb[(N + k) % D];
+        // one branch (gcn_zn); its ring's last refills request the next phase's first PFP fragments (nx)
+        gcn_zn<NTD, false, GD>(wr, vog, gl, L, gb, extra, Hs, pre, nx);
     } else {
         const int vo = lane_id() * 16;
         float4 wq[2][4];
@@ -1380,6 +1399,142 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         H[t] = relu4(Hs[t]);
         H[4 + t] = ZN ? H[t] : relu4(Ht[t]);
     }
+    TM_STAMP(5);
+}
+
+// The pair pass of the zero-node table-mode instances: positions 0 and 1 of a walk, which do not depend on each
+// other before the score, as two column sets (pi0 / et0 -> U0, pi1 / et1 -> U1) through ONE stream of lin_event's
+// weight fragments -- every ev3 fragment out of the ring feeds the six products of position 0's tile and the six of
+// position 1's, so a walk streams the split pack once, not twice.  Per column the arithmetic is encode_position's:
+// the same six products in the same order, the same K-step order, the accumulator starting from the same table row
+// (bit-identical results).  A tile's MFMAs are interleaved with its twin's in the other set (the independent chains
+// that the tile pairs supply in encode_position; 3 fragments live per step, not 6), and one element of both sets'
+// next-step features is generated between the MFMAs of a tile -- the same VALU work per MFMA.  event_gcn's first
+// layer then runs for the two sets one after the other (gcn_zn; the sets' accumulators, rings and split activations
+// together do not fit the register file), set 1's L kept live meanwhile and the g13 pack's streamed steps requested
+// once per set; `extra` is placed in set 1's layer.  On return pre holds nx's fragments.
+// Stamps: 1 table rows, 2 lin_event (both sets), 3 event_gcn set 0, 4 event_gcn set 1, 5 relu.
+template <int NQE, int NTD, int Q0, class Extra>
+__device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs,
+                                            const PosIn &pi0, const PosIn &pi1, const float4 (&et0)[NTD],
+                                            const float4 (&et1)[NTD], Extra &&extra, floatx4 (&U0)[4],
+                                            floatx4 (&U1)[4], float4 (&pre)[PFP], const NextFr &nx,
+                                            unsigned long long (&T)[10], const float4 *gl) {
+    static_assert(Q0 > 0, "the pair pass starts from the edge table's rows");
+    using C = WalkConsts<NQE, NTD>;
+    const EncW &P = a.P;
+    const int g = lane_id() >> 4;
+    const int de = P.de;
+    const float dt0 = pi0.v ? pi0.tb - pi0.ta : 0.f, c00 = pi0.v ? pi0.c0 : 0.f, c01 = pi0.v ? pi0.c1 : 0.f,
+                c02 = pi0.v ? pi0.c2 : 0.f;
+    const float dt1 = pi1.v ? pi1.tb - pi1.ta : 0.f, c10 = pi1.v ? pi1.c0 : 0.f, c11 = pi1.v ? pi1.c1 : 0.f,
+                c12 = pi1.v ? pi1.c2 : 0.f;
+    floatx4 L0[NTD], L1[NTD];
+#pragma unroll
+    for (int t = 0; t < NTD; ++t) {
+        L0[t] = floatx4{et0[t].x, et0[t].y, et0[t].z, et0[t].w};
+        L1[t] = floatx4{et1[t].x, et1[t].y, et1[t].z, et1[t].w};
+    }
+    TM_STAMP(1);
+    constexpr int NSG = (NTD + 1) / 2, GL = GCN_LDS;
+    const int vog = lane_id() * 16 + 16 * (int)(P.g13 - P.kv.w);
+    constexpr int GD = PAIR_GCN_RING;
+    float4 gb[GD];
+    {
+        // ring and fragment order as in encode_position (K-outer; fragment i = (step, tile, part)); the ring's last
+        // refills take the g13 pack's first streamed fragments for event_gcn
+        constexpr int NS = C::NS, S0 = Q0 / 2;
+        constexpr int N = NTD * (NS - S0) * 3, D = PAIR_LIN_RING;
+        static_assert(D >= PFP && D <= N && D % 3 == 0 && D <= GD, "lin_event ring depth");
+        const int vo3 = lane_id() * 16 + 16 * (int)(P.ev3 - P.kv.w);
+        auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
+        auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
+        int z3 = 0;
+        asm volatile("" : "+s"(z3));
+        auto wload3 = [&](int i) {
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i) * 16, 0));
+        };
+        auto wloadg = [&](int i) {
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, z3 + goff(i) * 16, 0));
+        };
+        float4 buf[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload3(i);
+        auto pure = [](int s) { return s > S0; };
+        const float *cw = cs + C::XW, *cp = cs + C::XP;
+        Split3 xs0, xs1;
+        {
+            float w8[8], p8[8];
+            lds8(cw, S0, w8);
+            lds8(cp, S0, p8);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                split_put(xs0, j, gen_one<true, false>(S0, j, w8[j], p8[j], 0.f, g, de, dt0, c00, c01, c02));
+                split_put(xs1, j, gen_one<true, false>(S0, j, w8[j], p8[j], 0.f, g, de, dt1, c10, c11, c12));
+            }
+        }
+#pragma unroll
+        for (int s = S0; s < NS; ++s) {
+            Split3 xn0 = xs0, xn1 = xs1;
+            // element j of step s + 1 of both sets, generated and split between this step's MFMAs (tiles 0..7); its
+            // frequency and phase are read from LDS where they are used (two sets of step features leave no
+            // registers for a step's 16 constants)
+            auto gen = [&](int j) {
+                if (s + 1 < NS && j < 8) {
+                    const float w = cw[32 * (s + 1) + 8 * g + j], ph = cp[32 * (s + 1) + 8 * g + j];
+                    const float v0 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02)
+                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02);
+                    const float v1 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12)
+                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12);
+                    split_put(xn0, j, v0);
+                    split_put(xn1, j, v1);
+                }
+            };
+            auto take = [&](int i) {
+                const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
+                if (i + D < N) buf[i % D] = wload3(i + D);
+                else buf[i % D] = wloadg(i + D - N);
+                return v;
+            };
+#pragma unroll
+            for (int t = 0; t < NTD; ++t) {
+                const int i = ((s - S0) * NTD + t) * 3;
+                const bf16x8 h = take(i), m = take(i + 1), l = take(i + 2);
+                L0[t] = TM_MF32(l, xs0.h, L0[t]);
+                L1[t] = TM_MF32(l, xs1.h, L1[t]);
+                L0[t] = TM_MF32(h, xs0.l, L0[t]);
+                L1[t] = TM_MF32(h, xs1.l, L1[t]);
+                L0[t] = TM_MF32(m, xs0.m, L0[t]);
+                L1[t] = TM_MF32(m, xs1.m, L1[t]);
+                L0[t] = TM_MF32(m, xs0.h, L0[t]);
+                L1[t] = TM_MF32(m, xs1.h, L1[t]);
+                L0[t] = TM_MF32(h, xs0.m, L0[t]);
+                L1[t] = TM_MF32(h, xs1.m, L1[t]);
+                L0[t] = TM_MF32(h, xs0.h, L0[t]);
+                L1[t] = TM_MF32(h, xs1.h, L1[t]);
+                gen(t);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            xs0 = xn0;
+            xs1 = xn1;
+        }
+#pragma unroll
+        for (int k = 0; k < GD; ++k) gb[k] = k < D ? buf[(N + k) % D] : wloadg(k);
+    }
+    TM_STAMP(2);
+    floatx4 Hs[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) Hs[t] = ldsx4(cs + C::G1, t);
+    gcn_zn<NTD, true, GD>(wr, vog, gl, L0, gb, [](int) {}, Hs, pre, nx);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) U0[t] = relu4(Hs[t]);
+    TM_STAMP(3);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) Hs[t] = ldsx4(cs + C::G1, t);
+    gcn_zn<NTD, false, GD>(wr, vog, gl, L1, gb, extra, Hs, pre, nx);
+    TM_STAMP(4);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) U1[t] = relu4(Hs[t]);
     TM_STAMP(5);
 }
 
@@ -1517,8 +1672,9 @@ __device__ __forceinline__ void walk_pool_head(const WalkArgs &a, __amdgpu_buffe
 }
 
 // this column's V . H (the 4 lane groups' parts summed); ZN: VZ . U over the first 4 tiles
-template <bool ZN = false>
-__device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const floatx4 (&H)[8]) {
+template <bool ZN = false, int NH>
+__device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const floatx4 (&H)[NH]) {
+    static_assert(NH >= (ZN ? 4 : 8), "a position's hidden vector");
     const int lane = threadIdx.x & 63;
     float s = 0.f;
 #pragma unroll
@@ -1531,7 +1687,7 @@ __device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const fl
 }
 
 // SPLIT (small grids, e.g. one reference batch per call in the drop-in surface): a wave takes one walk m of
-// its unit's 16 slots -- the slot pass, then that walk's positions 0 and 1 (3 passes instead of 1 + 2M) --
+// its unit's 16 slots -- the slot pass, then that walk's positions 0 and 1 (3 passes instead of 1 + 2M; PAIR: 2) --
 // so a unit's M walks run on M waves at once.  The slot pass is repeated by each of them (same values);
 // the chip is far from full at these sizes, and the latency of a call is one wave's pass chain.
 // (Running the three positions of an M == 1 unit on three waves at once, the stash and position 0's inputs
@@ -1540,8 +1696,13 @@ __device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const fl
 // POOL (tm_encoder_pool_fwd): a walk ends at attention.MLP's hidden layer (walk_pool_head); a slot's M weighted
 // hidden vectors are summed in registers and written as one partial per slot (SPLIT: one per walk, each wave
 // holding one walk of the slot) at a.out.
-template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false, bool POOL = false>
+// PAIR (the zero-node table-mode instances; tm_debug_set(TM_DEBUG_WALK_SINGLE, 1) selects the single-position
+// instances instead): a walk's positions 0 and 1 run in one pass as two column sets (encode_pair), so a unit is the
+// slot pass and one pass per walk -- 1 + M passes, SPLIT 2 -- and lin_event's weights are streamed once per walk.
+template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false, bool POOL = false,
+          bool PAIR = false>
 __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk_kernel(WalkArgs a) {
+    static_assert(!PAIR || (ZN && QE0 > 0 && !SEF && !POOL), "the pair pass: zero-node table mode, not pooled");
     using C = WalkConsts<NQE, NTD>;
     constexpr int NA = ZN ? 4 : 8;                      // tiles of a position's hidden vector (ZN: U alone)
     const EncW &P = a.P;
@@ -1612,7 +1773,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     // every weight fragment off one buffer resource (WalkLay offsets from the folded region's base)
     const auto wr = wrsrc(P.kv.w);
     // position 0's hidden vector (U_0 in the zero-node form) and score, carried to the position-1 pass; every
-    // position-0 pass overwrites both, so no unit reads another's
+    // position-0 pass overwrites both, so no unit reads another's (PAIR: not used, both positions are in one pass)
     floatx4 H0[NA];
     float s0 = 0.f;
     floatx4 PA[POOL ? 4 : 1];                           // POOL: sum of wgt_w h_w over the slot's walks so far
@@ -1620,10 +1781,13 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
 #pragma unroll
         for (int t = 0; t < 4; ++t) PA[t] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
-    const int n_pass = SPLIT ? 3 : 1 + 2 * a.M;
+    const int n_pass = PAIR ? (SPLIT ? 2 : 1 + a.M) : (SPLIT ? 3 : 1 + 2 * a.M);
     PosIn cur = load_pos(a, eg * a.W + (int64_t)j * a.M, 2, valid);
+    PosIn cur1 = cur;                                   // PAIR: position 1 of a pair pass (cur: position 0)
     float ef[EQ_MAX][4] = {};
     float4 et[ETAB_N(QE0)];
+    float4 et1[PAIR ? ETAB_N(QE0) : 1];                 // PAIR: position 1's table row
+    (void)cur1, (void)et1;
     // lin_event's first PFP fragments (ring order: tile 0's hi / mid / lo and tile 1's hi of its first 32-wide K
     // step QE0 / 2, in the split pack EncW::ev3), carried pass to pass
     NextFr lin0;
@@ -1648,9 +1812,11 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     int64_t egn = 0;
     int32_t jn = 0;
     if constexpr (!PERSIST) coords(unext, vn, egn, jn);
-    // pass 0: position 2 once per slot (walk j*M carries it); then per walk m: position 0, position 1
-#pragma nounroll
-    for (int pass = 0; pass < n_pass; ++pass) {
+    // pass 0: position 2 once per slot (walk j*M carries it); then per walk m: position 0, position 1 (PAIR: both
+    // in one pass, pass type 3)
+    // one pass of type pt (the loop body, inlined where it is called: once in the single-position instances;
+    // PAIR: the slot pass and the pair pass are two copies with pt a constant, so neither holds the other's state)
+    auto run_pass = [&](const int pass, const int pt) __attribute__((always_inline)) {
         if (PERSIST && pass + 1 == n_pass) {
             unext = ticket();
             coords(unext, vn, egn, jn);
@@ -1668,11 +1834,10 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             else if (q == 2) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
-        const int m = SPLIT ? m0 : pass == 0 ? 0 : (pass - 1) >> 1;
-        const int p = pass == 0 ? 2 : ((pass - 1) & 1);
+        const int m = SPLIT ? m0 : pass == 0 ? 0 : PAIR ? pass - 1 : (pass - 1) >> 1;
         const int64_t gw = eg * a.W + (int64_t)j * a.M + m;
         HeadIn hi{0.0, 1.f, 0.f, 0.f, -1, false};
-        auto load_hi = [&]() {                           // consumed by the head (p == 1); issued every pass, so
+        auto load_hi = [&]() {                           // consumed by the head (p == 1, 3); issued every pass, so
             hi.v = valid;                                // no branch holds the waits for them at the loads
             hi.cu = a.cut[eg];
             hi.sd = a.stdv[gw / a.BW];
@@ -1684,9 +1849,12 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
         // next pass's scalars (after the last pass: the next unit's slot pass); its edge features / table
         // row once this pass's lin_event is done
         const bool last = pass + 1 == n_pass;
-        const int pn = !last ? ((pass & 1) == 0 ? 0 : 1) : 2;
-        const int64_t gwn = !last ? eg * a.W + (int64_t)j * a.M + (SPLIT ? m0 : pass >> 1) : egn * a.W + (int64_t)jn * a.M;
-        PosIn nxt;
+        // (PAIR: both positions of walk m + 1; after the last pass position 1's are loaded too, of a valid row, and
+        // not used, so no branch surrounds the loads)
+        const int pn = !last ? (PAIR || (pass & 1) == 0 ? 0 : 1) : 2;
+        const int64_t gwn = !last ? eg * a.W + (int64_t)j * a.M + (SPLIT ? m0 : PAIR ? pass : pass >> 1)
+                                  : egn * a.W + (int64_t)jn * a.M;
+        PosIn nxt, nxt1;
         // the next pass's scalars (and the head's inputs of a position-1 pass) are requested inside event_gcn's
         // K loop at its first step (its weights are requested a whole step ahead there), not at the top of the
         // pass where lin_event's weight refills waited behind them
@@ -1694,11 +1862,30 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             if (q == 0) {
                 load_hi();
                 nxt = load_pos(a, gwn, pn, !last ? valid : vn);
+                if constexpr (PAIR) nxt1 = load_pos(a, gwn, 1, !last ? valid : vn);
             }
         };
-        floatx4 H[8];
         unsigned long long T[10];
         TM_STAMP(0);
+        if (PAIR && pt == 3) {
+            // both positions of walk m, both scores, the head; event_gcn hands off A1G's first fragments, the head
+            // the next pass's lin_event fragments
+            if constexpr (PAIR) {
+                floatx4 U0[4], U1[4];
+                encode_pair<NQE, NTD, QE0>(a, wr, cs, cur, cur1, et, et1, extra, U0, U1, pre,
+                                           pair_first<4>(FoldLay::A1GZ / 4), T, gl);
+                load_et<QE0>(a, nxt.edge(), et);
+                load_et<QE0>(a, nxt1.edge(), et1);
+                cur = nxt;
+                cur1 = nxt1;
+                TM_STAMP(6);
+                const float sc0 = score_dot<true>(st, U0), sc1 = score_dot<true>(st, U1);
+                TM_STAMP(7);
+                walk_head<NQE, NTD, true>(a, wr, cs, gw, valid, hi, st, sc0, sc1, U0, U1, pre, lin0);
+            }
+        } else {
+        const int p = PAIR ? 2 : pt;                     // PAIR: only the slot pass comes here
+        floatx4 H[8];
         // event_gcn hands off the pass's next GEMM's first fragments: the slot pass's A1D, the position-1 pass's
         // A1G (consumed in the head, after the softmax); a position-0 pass has no GEMM left, so the next pass's
         // lin_event fragments
@@ -1709,6 +1896,10 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
         if constexpr (QE0 == 0) load_ef(a, nxt.edge(), ef);
         else load_et<QE0>(a, nxt.edge(), et);
         cur = nxt;
+        if constexpr (PAIR) {
+            load_et<QE0>(a, nxt1.edge(), et1);
+            cur1 = nxt1;
+        }
         TM_STAMP(6);
         // ZN: H = [U; U]: the layers reading H as their 64-column-folded forms on U (FoldLay KVZ ...)
         floatx4 Uv[4];
@@ -1797,21 +1988,31 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             if constexpr (ZN) walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, Uv, pre, lin0);
             else walk_head<NQE, NTD, ZN>(a, wr, cs, gw, valid, hi, st, s0, s, H0, H, pre, lin0);
         }
+        }
         TM_STAMP(8);
 #ifdef TM_TRACE
         if (lane == 0 && trw < 8192 && trn < 2 && pass < 7) g_tr[trw][2 + 7 * trn + pass] = __builtin_amdgcn_s_memrealtime();
 #endif
 #ifdef TM_STAMPS
         if (lane == 0 && blockIdx.x % 16 == 5) {
-            for (int k = 0; k < 8; ++k) atomicAdd(&g_st[p][k], T[k + 1] - T[k]);
-            atomicAdd(&g_st[p][8], 1ull);
+            for (int k = 0; k < 8; ++k) atomicAdd(&g_st[pt][k], T[k + 1] - T[k]);
+            atomicAdd(&g_st[pt][8], 1ull);
         }
 #endif
+    };
+    if constexpr (PAIR) {
+        run_pass(0, 2);
+#pragma nounroll
+        for (int pass = 1; pass < n_pass; ++pass) run_pass(pass, 3);
+    } else {
+#pragma nounroll
+        for (int pass = 0; pass < n_pass; ++pass) run_pass(pass, pass == 0 ? 2 : ((pass - 1) & 1));
     }
 #ifdef TM_TRACE
     if (lane == 0 && trw < 8192) {
         if (trn < 12) g_tr[trw][16 + trn] = __builtin_amdgcn_s_memrealtime();
         g_tr[trw][28] = ++trn;
+        g_tr[trw][30] = (unsigned long long)n_pass;
     }
 #endif
     unit = unext;
@@ -2444,12 +2645,12 @@ constexpr int64_t WALK_SPLIT_UNITS = 512;
 static bool walk_split(int64_t units, int32_t M) { return units * M <= 3 * WALK_SPLIT_UNITS && units < WALK_SPLIT_UNITS; }
 
 // a.ticket zeroed on the stream before the launch unless walk_split (encoder_fwd_impl)
-template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false, bool POOL = false>
-static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
+template <int NQE, bool SEF, int Q0, bool ZN, bool POOL, bool PAIR>
+static void launch_walk_as(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     const int64_t units = (a.n_slots + 15) / 16;
     if (walk_split(units, a.M)) {
         const unsigned sb = (unsigned)((units * a.M + WALK_WPB - 1) / WALK_WPB);
-        walk_kernel<NQE, 11, SEF, Q0, true, ZN, POOL><<<dim3(sb), 64 * WALK_WPB, 0, s>>>(a);
+        walk_kernel<NQE, 11, SEF, Q0, true, ZN, POOL, PAIR><<<dim3(sb), 64 * WALK_WPB, 0, s>>>(a);
         return;
     }
     // one round of resident workgroups (occupancy x CUs of the current device), cached per instance
@@ -2458,7 +2659,7 @@ static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
         if (cap[dev] == 0) {
             int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL>, 64 * WALK_WPB, 0) ==
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR>, 64 * WALK_WPB, 0) ==
                     hipSuccess &&
                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0 &&
                 cus > 0)
@@ -2470,7 +2671,17 @@ static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     }
     const int dbg = debug_opt(TM_DEBUG_WALK_BLOCKS);   // A/B of smaller persistent grids (tools/walk_grid_ab.sh)
     if (dbg > 0 && blocks > (unsigned)dbg) blocks = (unsigned)dbg;
-    walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL><<<dim3(blocks), 64 * WALK_WPB, 0, s>>>(a);
+    walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR><<<dim3(blocks), 64 * WALK_WPB, 0, s>>>(a);
+}
+
+// the zero-node table-mode instances run the pair pass unless tm_debug_set(TM_DEBUG_WALK_SINGLE, 1) asks for the
+// single-position pass (tests compare the two bit for bit)
+template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false, bool POOL = false>
+static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
+    if constexpr (ZN && Q0 > 0 && !SEF && !POOL) {
+        if (!debug_opt(TM_DEBUG_WALK_SINGLE)) return launch_walk_as<NQE, SEF, Q0, ZN, POOL, true>(a, blocks, s);
+    }
+    launch_walk_as<NQE, SEF, Q0, ZN, POOL, false>(a, blocks, s);
 }
 
 extern "C" int tm_encoder_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
@@ -3190,7 +3401,7 @@ extern "C" int tm_debug_trace(unsigned long long *host) {
 #endif
 #ifdef TM_STAMPS
 extern "C" int tm_debug_stamps(unsigned long long *host) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(tmk::g_st), sizeof(unsigned long long) * 30, 0,
+    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(tmk::g_st), sizeof(unsigned long long) * 40, 0,
                                     hipMemcpyDeviceToHost);
 }
 #endif

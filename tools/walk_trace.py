@@ -43,9 +43,12 @@ def summarise(tr, n_waves):
     two = used & (n >= 2)
     if two.any():
         st = np.concatenate([tr[two, 1:2], tr[two, 2:16]], axis=1).astype(np.int64)
-        d = np.diff(st, axis=1) * 0.01
-        print("  unit 0 passes (us, median):", " ".join(f"{np.median(d[:, i]):.1f}" for i in range(7)))
-        print("  unit 1 passes (us, median):", " ".join(f"{np.median(d[:, 7 + i]):.1f}" for i in range(7)))
+        # passes per unit: 1 + 2M, or 1 + M where a walk's positions 0 / 1 share a pair pass (an older build: 7)
+        npass = min(7, int(tr[two, 30].max()) or 7)
+        u0 = np.diff(st[:, :1 + npass], axis=1) * 0.01
+        u1 = np.diff(np.concatenate([st[:, npass:npass + 1], st[:, 8:8 + npass]], axis=1), axis=1) * 0.01
+        print("  unit 0 passes (us, median):", " ".join(f"{np.median(u0[:, i]):.1f}" for i in range(npass)))
+        print("  unit 1 passes (us, median):", " ".join(f"{np.median(u1[:, i]):.1f}" for i in range(npass)))
     hw = tr[:, 29].astype(np.uint64)
     xcc = (hw >> np.uint64(32)) & np.uint64(0xF)
     simd = (hw >> np.uint64(4)) & np.uint64(0x3)

@@ -609,7 +609,7 @@ int tm_edge_importance_tab(const float *gf, int32_t n_ids, int32_t n_groups, int
  * side (same result up to fp32 reassociation; DESIGN.md "TGN contrast"). */
 typedef struct {
     int32_t rows, n_ngh, n_head;
-    int32_t d_node, d_edge, d_time;       /* d_key = d_node + d_edge + d_time <= 512 */
+    int32_t d_node, d_edge, d_time;       /* d_key = d_node + d_edge + d_time <= 576 (training pair: 512) */
     int32_t node_rows, edge_rows;         /* table sizes when gathered (index checks) */
     int32_t head_major_rows;              /* 1 = the reference's row pairing (see above) */
     int32_t seg_rows;                     /* > 0: rows are independent batches of seg_rows rows and the
@@ -627,7 +627,8 @@ typedef struct {
     int32_t *err_flag;                    /* nullable device flag: set to TM_E_ARG on an out-of-range index */
 } tm_tgn_attn;
 
-/* forward: z [rows, n_head*d_key], stats [rows, n_head, 2] (softmax max and sum, for the backward) */
+/* forward: z [rows, n_head*d_key], stats [rows, n_head, 2] (softmax max and sum, for the backward).
+ * Limits of the pair: n_head <= 4, d_key <= 576 (nine key registers per lane), else TM_E_UNSUPPORTED. */
 int tm_tgn_attn_fwd(const tm_tgn_attn *a, float *z, float *stats, void *stream);
 /* backward given gz = dL/dz: d_ew_parts [rows*n_head, n_ngh] holds the contribution of pair
  * q = r*n_head + h to d ew[m(q), j] (the caller sums the n_head contributions of each row);
@@ -641,7 +642,8 @@ int tm_tgn_attn_bwd(const tm_tgn_attn *a, const float *stats, const float *gz, f
  * neighbour j) at (r*n_head + h)*n_ngh + j -- the layout of the reference's dropped tensor:
  *     z[r,h] = sum_j softmax(s)_j * keep_j * keep_scale * ew[m,j] * key[r,j]
  * stats holds the plain softmax's max and sum.  With keep == NULL, z and stats are tm_tgn_attn_fwd's bits.
- * Limits: those of tm_tgn_attn_fwd, and tm_tgn_attn_bwd's bound on n_ngh (TM_E_UNSUPPORTED). */
+ * Limits: those of tm_tgn_attn_fwd except d_key <= 512 (the training kernels of this layer, _fwd, _bwd and _dtab,
+ * stop at eight key registers: a wider key is TM_E_UNSUPPORTED), and tm_tgn_attn_bwd's bound on n_ngh. */
 int tm_tgn_attn_train_fwd(const tm_tgn_attn *a, const uint8_t *keep, float keep_scale, float *z, float *stats,
                           void *stream);
 /* backward: tm_tgn_attn_bwd with e'_j = ew_j * keep_j * keep_scale for ew_j (d_ew_parts, nullable, holds
@@ -688,7 +690,7 @@ int tm_tgn_rows_reduce(const float *grad, int64_t n_rows, int32_t d, const int64
  * pairing of :128-130 inside the rows of one forward_msg call; m = r when head_major_rows is 0.
  * qf[r,h] = (W_k,h^T W_q,h) query[r] with query = [src | 0 | src_t]; d_key = d_node + d_edge + d_time is
  * the model width (each head projects it to d_key / n_head), temperature = sqrt(d_key / n_head).
- * Limits: n_head <= 4, d_key <= 512 (else TM_E_UNSUPPORTED).  Out-of-range node / edge ids set *err_flag
+ * Limits: n_head <= 4, d_key <= 576 (else TM_E_UNSUPPORTED).  Out-of-range node / edge ids set *err_flag
  * and read row 0.  Field meanings as in tm_tgn_attn. */
 typedef struct {
     int32_t rows, n_ngh, n_head;
@@ -726,7 +728,8 @@ int tm_tgat_attn_bwd(const tm_tgat_attn *a, const float *stats, const float *gz,
  * [B*N_src*n_head, 1, N]; 1 = kept, a kept probability is scaled by keep_scale = 1 / (1 - p):
  *     z[r,h] = sum_j softmax(s)_j * keep_j * keep_scale * ew[m,j] * key[r,j]
  * stats holds the plain softmax's max and sum.  With keep == NULL, z and stats are tm_tgat_attn_fwd's bits.
- * Limits: those of tm_tgat_attn_fwd, and tm_tgat_attn_bwd's bound on n_ngh (TM_E_UNSUPPORTED). */
+ * Limits: those of tm_tgat_attn_fwd (d_key <= 576 here too), and tm_tgat_attn_bwd's bound on n_ngh
+ * (TM_E_UNSUPPORTED). */
 int tm_tgat_attn_train_fwd(const tm_tgat_attn *a, const uint8_t *keep, float keep_scale, float *z, float *stats,
                            void *stream);
 /* backward: tm_tgat_attn_bwd with e'_j = ew_j * keep_j * keep_scale for ew_j (d_ew_parts, nullable, holds
@@ -748,7 +751,7 @@ int64_t tm_tgat_attn_train_workspace_bytes(int64_t rows, int32_t d_time);
  *     h   = LayerNorm(u) * ln_w + ln_b          over d_key, eps 1e-5
  *     out = W21 relu(W11 h + b11) + b21 + W22 relu(W12 src + b12) + b22       src = query[:, :feat]
  * Every weight is passed TRANSPOSED ([in][out] row-major): gt [n_head*d_key, d_key], w11t [d_key, feat],
- * w12t / w21t / w22t [feat, feat].  out [rows, feat].  feat <= d_key <= 512, and the row tile
+ * w12t / w21t / w22t [feat, feat].  out [rows, feat].  feat <= d_key <= 576, and the row tile
  * (16 rows of d_key + 2 max(feat, 128) padded columns) must fit 64 KiB of LDS, else TM_E_UNSUPPORTED. */
 typedef struct {
     int32_t rows, n_head, d_key, feat;

@@ -292,7 +292,8 @@ __global__ void __launch_bounds__(64 * ATT_WAVES) tgat_attn_bwd_kernel(tm_tgat_a
 constexpr int MG_ROWS = 16;      // rows per workgroup = one MFMA row tile
 constexpr int MG_WAVES = 4;
 constexpr int MG_KC = 128;       // K chunk of the z G^T product staged through LDS
-constexpr int MG_MAXT = 8;       // column tiles per wave: 16 * MG_WAVES * MG_MAXT = 512 columns
+constexpr int MG_MAXT = 9;       // most column tiles per wave: 16 * MG_WAVES * MG_MAXT = 576 columns; the kernel is
+                                 // instantiated for 8 tiles (d_key <= 512, the code it always was) and for 9
 constexpr int MG_PAD = 4;        // row stride padding of the LDS tiles (floats)
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -302,8 +303,9 @@ __host__ __device__ inline int mg_up16(int x) { return (x + 15) & ~15; }
 // acc[t] += A[16][k0..k0+kn) (LDS, row stride lda, kn a multiple of 16, zero-padded) * BT[kg0 + k][n] for the
 // wave's column tiles nt = wave + MG_WAVES t.  Within a 16-deep step lane l feeds k = 4 (l >> 4) + s to the
 // s-th MFMA on both operands (any order of k is the same sum of products per MFMA step).
+template <int MAXT>
 __device__ __forceinline__ void mg_gemm(const float *A, int lda, int kn, const float *__restrict__ BT, int kg0, int K,
-                                        int N, floatx4 acc[MG_MAXT]) {
+                                        int N, floatx4 acc[MAXT]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int arow = lane & 15, ak = 4 * (lane >> 4);
     const int nt_n = (N + 15) >> 4;
@@ -312,7 +314,7 @@ __device__ __forceinline__ void mg_gemm(const float *A, int lda, int kn, const f
         const float a4[4] = {av.x, av.y, av.z, av.w};
         const int kg = kg0 + k0 + ak;
 #pragma unroll
-        for (int t = 0; t < MG_MAXT; ++t) {
+        for (int t = 0; t < MAXT; ++t) {
             const int nt = wave + MG_WAVES * t;
             if (nt < nt_n) {
                 const int n = nt * 16 + arow;
@@ -326,18 +328,19 @@ __device__ __forceinline__ void mg_gemm(const float *A, int lda, int kn, const f
     }
 }
 
-__device__ __forceinline__ void mg_zero(floatx4 acc[MG_MAXT]) {
+template <int MAXT>
+__device__ __forceinline__ void mg_zero(floatx4 acc[MAXT]) {
 #pragma unroll
-    for (int t = 0; t < MG_MAXT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < MAXT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
 }
 
 // epilogue: f(row in tile, column, value) for every element this lane holds of its wave's column tiles
-template <class F>
-__device__ __forceinline__ void mg_epi(const floatx4 acc[MG_MAXT], int N, F f) {
+template <int MAXT, class F>
+__device__ __forceinline__ void mg_epi(const floatx4 acc[MAXT], int N, F f) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int nt_n = (N + 15) >> 4;
 #pragma unroll
-    for (int t = 0; t < MG_MAXT; ++t) {
+    for (int t = 0; t < MAXT; ++t) {
         const int nt = wave + MG_WAVES * t;
         if (nt < nt_n) {
             const int n = nt * 16 + (lane & 15);
@@ -349,6 +352,7 @@ __device__ __forceinline__ void mg_epi(const floatx4 acc[MG_MAXT], int N, F f) {
     }
 }
 
+template <int MAXT>
 __global__ void __launch_bounds__(64 * MG_WAVES) tgat_merge_fwd_kernel(tm_tgat_merge a, float *__restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int dk = a.d_key, F = a.feat, K1 = a.n_head * a.d_key;
@@ -360,10 +364,10 @@ __global__ void __launch_bounds__(64 * MG_WAVES) tgat_merge_fwd_kernel(tm_tgat_m
     float *T2 = T1 + MG_ROWS * ldt;      // [16][ldt]  relu(W12 src + b12)
     const int tid = threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * MG_ROWS;
-    floatx4 acc[MG_MAXT];
+    floatx4 acc[MAXT];
 
     // u = z G^T: z in K chunks through T1
-    mg_zero(acc);
+    mg_zero<MAXT>(acc);
     for (int kc = 0; kc < K1; kc += MG_KC) {
         const int kn = K1 - kc < MG_KC ? mg_up16(K1 - kc) : MG_KC;
         __syncthreads();
@@ -373,9 +377,9 @@ __global__ void __launch_bounds__(64 * MG_WAVES) tgat_merge_fwd_kernel(tm_tgat_m
             T1[r * ldt + c] = ok ? a.z[(row0 + r) * K1 + kc + c] : 0.f;
         }
         __syncthreads();
-        mg_gemm(T1, ldt, kn, a.gt, kc, K1, dk, acc);
+        mg_gemm<MAXT>(T1, ldt, kn, a.gt, kc, K1, dk, acc);
     }
-    mg_epi(acc, dk, [&](int r, int n, float v) {
+    mg_epi<MAXT>(acc, dk, [&](int r, int n, float v) {
         const float qv = row0 + r < a.rows ? a.query[(row0 + r) * dk + n] : 0.f;
         U[r * ldu + n] = v + a.fc_b[n] + qv;
     });
@@ -408,14 +412,14 @@ __global__ void __launch_bounds__(64 * MG_WAVES) tgat_merge_fwd_kernel(tm_tgat_m
     __syncthreads();
 
     // T2 = relu(src W12^T + b12)
-    mg_zero(acc);
-    mg_gemm(T1, ldt, fp, a.w12t, 0, F, F, acc);
-    mg_epi(acc, F, [&](int r, int n, float v) { T2[r * ldt + n] = fmaxf(v + a.b12[n], 0.f); });
+    mg_zero<MAXT>(acc);
+    mg_gemm<MAXT>(T1, ldt, fp, a.w12t, 0, F, F, acc);
+    mg_epi<MAXT>(acc, F, [&](int r, int n, float v) { T2[r * ldt + n] = fmaxf(v + a.b12[n], 0.f); });
     __syncthreads();      // every wave is done reading src before T1 is rewritten
     // T1 = relu(h W11^T + b11)
-    mg_zero(acc);
-    mg_gemm(U, ldu, dkp, a.w11t, 0, dk, F, acc);
-    mg_epi(acc, F, [&](int r, int n, float v) { T1[r * ldt + n] = fmaxf(v + a.b11[n], 0.f); });
+    mg_zero<MAXT>(acc);
+    mg_gemm<MAXT>(U, ldu, dkp, a.w11t, 0, dk, F, acc);
+    mg_epi<MAXT>(acc, F, [&](int r, int n, float v) { T1[r * ldt + n] = fmaxf(v + a.b11[n], 0.f); });
     // zero the K padding of both tiles (columns F..fp-1 were never written by the epilogues)
     for (int i = tid; i < MG_ROWS * (fp - F); i += 64 * MG_WAVES) {
         const int r = i / (fp - F), c = F + i % (fp - F);
@@ -425,10 +429,10 @@ __global__ void __launch_bounds__(64 * MG_WAVES) tgat_merge_fwd_kernel(tm_tgat_m
     __syncthreads();
 
     // out = T1 W21^T + T2 W22^T + b21 + b22
-    mg_zero(acc);
-    mg_gemm(T1, ldt, fp, a.w21t, 0, F, F, acc);
-    mg_gemm(T2, ldt, fp, a.w22t, 0, F, F, acc);
-    mg_epi(acc, F, [&](int r, int n, float v) {
+    mg_zero<MAXT>(acc);
+    mg_gemm<MAXT>(T1, ldt, fp, a.w21t, 0, F, F, acc);
+    mg_gemm<MAXT>(T2, ldt, fp, a.w22t, 0, F, F, acc);
+    mg_epi<MAXT>(acc, F, [&](int r, int n, float v) {
         if (row0 + r < a.rows) out[(row0 + r) * F + n] = v + a.b21[n] + a.b22[n];
     });
 }
@@ -453,7 +457,7 @@ static int check_attn(const tm_tgat_attn *a, const char *who) {
         return fail(TM_E_ARG, std::string(who) + ": bad sizes");
     if (a->n_head > ATT_MAXH) return fail(TM_E_UNSUPPORTED, std::string(who) + ": n_head > 4");
     const int dk = a->d_node + a->d_edge + a->d_time;
-    if (dk > 64 * 8) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 512");
+    if (dk > 64 * 9) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 576");
     if (a->rows == 0) return TM_OK;
     if (!a->node_tab || (a->d_edge && !a->edge_tab) || !a->dt || (a->d_time && (!a->time_w || !a->time_b)) ||
         !a->mask_node || !a->qf)
@@ -506,7 +510,8 @@ static void launch_bwd(const tm_tgat_attn &a, const float *stats, const float *g
         case 5: CALL(5); break;          \
         case 6: CALL(6); break;          \
         case 7: CALL(7); break;          \
-        default: CALL(8); break;         \
+        case 8: CALL(8); break;          \
+        default: CALL(9); break;         \
     }
 
 extern "C" int tm_tgat_attn_fwd(const tm_tgat_attn *a, float *z, float *stats, void *stream) {
@@ -547,7 +552,7 @@ extern "C" int tm_tgat_merge_fwd(const tm_tgat_merge *a, float *out, void *strea
     if (!a) return fail(TM_E_ARG, "tm_tgat_merge_fwd: NULL descriptor");
     if (a->rows < 0 || a->n_head < 1 || a->d_key <= 0 || a->feat <= 0 || a->feat > a->d_key)
         return fail(TM_E_ARG, "tm_tgat_merge_fwd: bad sizes");
-    if (a->d_key > 16 * MG_WAVES * MG_MAXT) return fail(TM_E_UNSUPPORTED, "tm_tgat_merge_fwd: d_key > 512");
+    if (a->d_key > 16 * MG_WAVES * MG_MAXT) return fail(TM_E_UNSUPPORTED, "tm_tgat_merge_fwd: d_key > 576");
     const size_t lds = mg_lds_bytes(a->d_key, a->feat);
     if (lds > 64 * 1024)
         return fail(TM_E_UNSUPPORTED, "tm_tgat_merge_fwd: the row tile of d_key + 2 feat columns exceeds 64 KiB of LDS");
@@ -558,7 +563,9 @@ extern "C" int tm_tgat_merge_fwd(const tm_tgat_merge *a, float *out, void *strea
     hipStream_t s = (hipStream_t)stream;
     const unsigned blocks = (unsigned)(((int64_t)a->rows + MG_ROWS - 1) / MG_ROWS);
     hipEvent_t pe = prof_begin(s);
-    tgat_merge_fwd_kernel<<<dim3(blocks), 64 * MG_WAVES, lds, s>>>(*a, out);
+    // 8 column tiles per wave cover d_key <= 512; only the wider keys pay for the ninth accumulator
+    if (a->d_key <= 16 * MG_WAVES * 8) tgat_merge_fwd_kernel<8><<<dim3(blocks), 64 * MG_WAVES, lds, s>>>(*a, out);
+    else tgat_merge_fwd_kernel<MG_MAXT><<<dim3(blocks), 64 * MG_WAVES, lds, s>>>(*a, out);
     TM_CHECK_LAUNCH();
     prof_end("tgat_merge_fwd_kernel", s, pe);
     return TM_OK;

@@ -386,7 +386,7 @@ static int check_train(const tm_tgat_attn *a, const char *who) {
         return fail(TM_E_ARG, std::string(who) + ": bad sizes");
     if (a->n_head > ATT_MAXH) return fail(TM_E_UNSUPPORTED, std::string(who) + ": n_head > 4");
     const int dk = a->d_node + a->d_edge + a->d_time;
-    if (dk > 64 * 8) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 512");
+    if (dk > 64 * 9) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 576");
     if ((size_t)3 * a->n_ngh * ATT_MAXH * ATT_WAVES * sizeof(float) > 64 * 1024)
         return fail(TM_E_UNSUPPORTED, std::string(who) + ": n_ngh too large");
     if (a->rows == 0) return TM_OK;
@@ -445,7 +445,8 @@ static void launch_train_bwd(const tm_tgat_attn &a, const uint8_t *keep, float k
         case 5: CALL(5); break;                \
         case 6: CALL(6); break;                \
         case 7: CALL(7); break;                \
-        default: CALL(8); break;               \
+        case 8: CALL(8); break;                \
+        default: CALL(9); break;               \
     }
 
 extern "C" int64_t tm_tgat_attn_train_workspace_bytes(int64_t rows, int32_t d_time) {

@@ -279,7 +279,7 @@ static int check_attn(const tm_tgn_attn *a, const char *who) {
         a->d_time < 0 || !(a->temperature > 0.f))
         return fail(TM_E_ARG, std::string(who) + ": bad sizes");
     const int dk = a->d_node + a->d_edge + a->d_time;
-    if (dk > 64 * 8) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 512");
+    if (dk > 64 * 9) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 576");
     if (a->rows == 0) return TM_OK;
     if (!a->node_tab || (a->d_edge && !a->edge_tab) || !a->dt || (a->d_time && (!a->time_w || !a->time_b)) ||
         !a->mask_node || !a->qf)
@@ -329,7 +329,7 @@ extern "C" int tm_tgn_attn_fwd(const tm_tgn_attn *a, float *z, float *stats, voi
     const int kpl = (a->d_node + a->d_edge + a->d_time + 63) / 64;
     hipEvent_t pe = prof_begin(s);
 #define TM_FWD(K) launch_fwd<K>(*a, z, stats, s)
-    TM_KPL_DISPATCH(kpl, TM_FWD)
+    TM_KPL_DISPATCH9(kpl, TM_FWD)
 #undef TM_FWD
     TM_CHECK_LAUNCH();
     prof_end("tgn_attn_fwd_kernel", s, pe);
@@ -348,7 +348,7 @@ extern "C" int tm_tgn_attn_bwd(const tm_tgn_attn *a, const float *stats, const f
     const int kpl = (a->d_node + a->d_edge + a->d_time + 63) / 64;
     hipEvent_t pe = prof_begin(s);
 #define TM_BWD(K) launch_bwd<K>(*a, stats, gz, d_ew_parts, d_node, s)
-    TM_KPL_DISPATCH(kpl, TM_BWD)
+    TM_KPL_DISPATCH9(kpl, TM_BWD)
 #undef TM_BWD
     TM_CHECK_LAUNCH();
     prof_end("tgn_attn_bwd_kernel", s, pe);

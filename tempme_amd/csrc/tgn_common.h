@@ -99,3 +99,11 @@ __device__ __forceinline__ int64_t pair_row(const tm_tgn_attn &a, int64_t r, int
         case 7: CALL(7); break;     \
         default: CALL(8); break;    \
     }
+
+// the same with a ninth register (d_key up to 576): the frozen attention pair of tgn_attn.hip only; the training
+// kernels of tgn_train.hip stop at 8
+#define TM_KPL_DISPATCH9(KPLV, CALL)               \
+    switch (KPLV) {                                \
+        case 9: CALL(9); break;                    \
+        default: TM_KPL_DISPATCH(KPLV, CALL) break; \
+    }

@@ -310,8 +310,8 @@ class TGAT(nn.Module):
         self.e_feat_dim = self.e_feat_th.shape[1]
         self.time_dim = self.feat_dim
         self.model_dim = self.feat_dim + self.e_feat_dim + self.time_dim
-        if self.model_dim > 512:
-            raise NotImplementedError(f"model_dim {self.model_dim}: the attention kernels hold keys of at most 512")
+        if self.model_dim > 576:
+            raise NotImplementedError(f"model_dim {self.model_dim}: the attention kernels hold keys of at most 576")
         self.dropout_p = drop_out
         self.edge_raw_embed = nn.Embedding.from_pretrained(self.e_feat_th, padding_idx=0, freeze=True)
         self.node_raw_embed = nn.Embedding.from_pretrained(self.n_feat_th, padding_idx=0, freeze=True)

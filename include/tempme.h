@@ -770,6 +770,21 @@ int tm_tgat_merge_fwd(const tm_tgat_merge *a, float *out, void *stream);
 int tm_mask_least_important(const float *imp, int32_t rows, int32_t n, const int32_t *k_of_group, int32_t n_groups,
                             const int32_t *node_in, int32_t *node_out, void *stream);
 
+/* Per-batch evaluation metrics (sklearn.metrics.average_precision_score / roc_auc_score as
+ * temp_exp_main.py:463-478, :253-263, :633-649 and learn_base.py:43-73 call them per batch) for n_vec score
+ * vectors of length n, one workgroup each.  A label is positive iff it is > 0.5; with P positives, Nn = n - P and
+ * ge_i = #{j: s_j >= s_i}, pge_i = #{j positive: s_j >= s_i}, pgt_i = #{j positive: s_j > s_i}:
+ *   AP  = (1 / P) sum_{i positive} pge_i / ge_i               (0.0 when P = 0, as scikit-learn)
+ *   AUC = sum_{i negative} (pgt_i + pge_i) / (2 P Nn)         (NaN when P = 0 or Nn = 0, as scikit-learn 1.7)
+ * Scores are compared as the fp32 values given (ties count as ties, -0.0 == 0.0); a NaN score makes both figures
+ * of its vector NaN (scikit-learn raises there).  Integer counts, fp64 sums in a fixed order: the same bits from
+ * every launch.  n <= 8192 (TM_E_UNSUPPORTED beyond); n <= 0, n_vec < 0 or a row stride below n: TM_E_ARG;
+ * n_vec = 0 is a no-op.
+ * out [n_vec][2] doubles: AP, ROC-AUC.  score rows score_stride floats apart (>= n);
+ * label_stride 0 = one label vector for all rows. */
+int tm_rank_metrics(const float *score, int64_t score_stride, const float *label, int64_t label_stride,
+                    int32_t n_vec, int32_t n, double *out, void *stream);
+
 /* ---------------------------------------------------------------- per-kernel timing
  * tm_profile_enable(1) clears and starts recording a HIP event pair around every kernel
  * launch, on that launch's stream; tm_profile_sync() waits and aggregates, returning the

@@ -13,6 +13,7 @@ from ._lib import SIDE_BGD, SIDE_NONE, SIDE_SRC, SIDE_TGT, SPLIT_NULL, SPLIT_TES
 from .batch_loader import RandEdgeSampler  # noqa: F401
 from .explainer import TempME, compute_node_degrees  # noqa: F401
 from .graph import NeighborFinder, adjacency_from_edges  # noqa: F401
+from .metrics import rank_metrics  # noqa: F401
 from .null_model import degree_dict, get_null_distribution, load_data_shuffle  # noqa: F401
 from .preprocess import calculate_edge, marginal, pre_processing  # noqa: F401
 from .tgat import TGAT  # noqa: F401

@@ -20,6 +20,11 @@ the end brings every rank's [k, 13 figures] rows to every rank, which sorts them
 means in the reference's batch order -- the same floating-point sums as one process.  With
 ``if_bern`` (Beta rsample inside retrieve_explanation) the draws come from torch's device RNG; pass
 ``seed`` to reseed it per batch (seed + k) so the draws, too, do not depend on the shard.
+
+By default a batch's AP and AUC come from scikit-learn on the host, as in the reference (one copy of the
+scores and several scalar reads per batch).  With ``device_metrics=True`` they come from
+``metrics.rank_metrics`` (tm_rank_metrics), the batch's row stays a device tensor and the epoch copies the
+stacked rows to the host once.
 """
 import math
 
@@ -63,9 +68,13 @@ def _metrics_sklearn(y, yp):
     return average_precision_score(y, yp), roc_auc_score(y, yp)
 
 
-def eval_batch(args, base_model, explainer, batch):
+def eval_batch(args, base_model, explainer, batch, device_metrics=False):
     """The figures of one reference batch (temp_exp_main.py:440-494) as a float64 [14] row: FIGURES (ratio
-    figures NaN unless ``args.test_threshold``) and the THRESHOLD_RAN flag."""
+    figures NaN unless ``args.test_threshold``) and the THRESHOLD_RAN flag.
+
+    ``device_metrics``: the row is a float64 device tensor built from the same fp32 tensors the host path reads,
+    with ``metrics.rank_metrics`` for aps / auc (and inside threshold_test); the batch then copies nothing to the
+    host, waits for nothing and calls no scikit-learn."""
     from . import fidelity
     criterion = torch.nn.BCEWithLogitsLoss()
     row = np.full(len(FIGURES) + 1, np.nan)
@@ -93,6 +102,20 @@ def eval_batch(args, base_model, explainer, batch):
                              dim=0).mean(0)
         fid_logit = torch.cat([pos_logit - pos_out_ori, neg_out_ori - neg_logit], dim=0).mean(0)
         acc = (pred_label == y_ori).float().mean()
+        if device_metrics:
+            from .metrics import rank_metrics
+            dev = y_pred.device
+            head = torch.stack([x.reshape(()) for x in (acc, fid_prob, fid_logit, loss, pred_loss, kl_loss)]).double()
+            if getattr(args, "test_threshold", False):
+                expl0 = explain_sides(explainer, batch, imps, False)
+                ratio = fidelity.threshold_test(args, expl0, base_model, batch.src, batch.dst, batch.fake, batch.ts,
+                                                batch.e_idx, pos_out_ori, neg_out_ori, y_ori, sg_s, sg_t, sg_b,
+                                                device_metrics=True)
+                ran = torch.ones(1, dtype=torch.float64, device=dev)
+            else:
+                ratio = torch.full((len(RATIO_FIGURES),), float("nan"), dtype=torch.float64, device=dev)
+                ran = torch.zeros(1, dtype=torch.float64, device=dev)
+            return torch.cat([rank_metrics(y_ori.reshape(-1), y_pred.reshape(-1)).reshape(2), head, ratio, ran])
         y_h, yp_h = y_ori.cpu().numpy(), y_pred.cpu().numpy()
         aps, auc = _metrics_sklearn(y_h, yp_h)
         row[:8] = (aps, auc, float(acc), float(fid_prob), float(fid_logit), float(loss), float(pred_loss),
@@ -109,20 +132,38 @@ def eval_batch(args, base_model, explainer, batch):
 def gather_rows(rows, world=1, group=None, device=None, collective=None):
     """Every rank's {k: row} (rows of equal length) on every rank, as one [n, 1 + F] float64 array sorted by
     batch index k.  One all_gather of a fixed-size padded tensor (RCCL needs device tensors: ``device``);
-    ``collective`` forces (True) or skips (False) the gather, default: world > 1."""
+    ``collective`` forces (True) or skips (False) the gather, default: world > 1.
+
+    Rows may be tensors (``eval_batch(device_metrics=True)``): they are stacked where they live and cross to the
+    host in one copy, after the all_gather when that runs on their device."""
     F = len(next(iter(rows.values()))) if rows else len(FIGURES)
-    mine = np.full((len(rows), 1 + F), np.nan)
-    for i, (k, r) in enumerate(sorted(rows.items())):
-        mine[i, 0], mine[i, 1:] = k, r
-    if (world > 1) if collective is None else collective:
+    gather = (world > 1) if collective is None else collective
+    mine_t = None
+    if rows and all(torch.is_tensor(r) for r in rows.values()):
+        order = sorted(rows)
+        body = torch.stack([rows[k].reshape(F).double() for k in order])
+        keys = torch.tensor(order, dtype=torch.float64).reshape(-1, 1)
+        mine_t = torch.cat([keys.to(body.device, non_blocking=True), body], dim=1)
+        if not gather or device is None or mine_t.device != torch.device(device):
+            mine_t = mine_t.cpu()           # the epoch's one device-to-host copy
+        mine = mine_t.numpy() if mine_t.device.type == "cpu" else None
+    else:
+        mine = np.full((len(rows), 1 + F), np.nan)
+        for i, (k, r) in enumerate(sorted(rows.items())):
+            mine[i, 0], mine[i, 1:] = k, (r.detach().cpu().numpy() if torch.is_tensor(r) else r)
+    if gather:
         dev = device if device is not None else torch.device("cpu")
         n = torch.tensor([len(rows)], dtype=torch.int64, device=dev)
         counts = [torch.zeros_like(n) for _ in range(world)]
         dist.all_gather(counts, n, group=group)
         cap = max(int(c.item()) for c in counts)
-        pad = np.full((cap, 1 + F), -1.0)
-        pad[:len(rows)] = mine
-        t = torch.from_numpy(pad).to(dev)
+        if mine is None:                    # device rows, device collective: padded on the device
+            t = torch.full((cap, 1 + F), -1.0, dtype=torch.float64, device=dev)
+            t[:len(rows)] = mine_t
+        else:
+            pad = np.full((cap, 1 + F), -1.0)
+            pad[:len(rows)] = mine
+            t = torch.from_numpy(pad).to(dev)
         parts = [torch.empty_like(t) for _ in range(world)]
         dist.all_gather(parts, t, group=group)
         allr = np.concatenate([p.cpu().numpy()[:int(c.item())] for p, c in zip(parts, counts)])
@@ -158,17 +199,22 @@ def reduce_epoch(allr):
 
 def run_sharded(spans, fn, rank=0, world=1, group=None, device=None):
     """``fn(k, start, end) -> row`` over this rank's whole batches, then every rank's rows gathered and
-    reduced (the control flow of eval_one_epoch with the batch loop sharded)."""
-    rows = {k: np.asarray(fn(k, s, e), dtype=np.float64) for k, s, e in shard_spans(spans, rank, world)}
+    reduced (the control flow of eval_one_epoch with the batch loop sharded).  A row that is a tensor stays
+    where it is until the gather."""
+    rows = {}
+    for k, s, e in shard_spans(spans, rank, world):
+        r = fn(k, s, e)
+        rows[k] = r if torch.is_tensor(r) else np.asarray(r, dtype=np.float64)
     return reduce_epoch(gather_rows(rows, world, group, device))
 
 
 def eval_one_epoch(args, base_model, explainer, buf, src, dst, ts, e_idx, *, rank=0, world=1, group=None,
-                   seed=None):
+                   seed=None, device_metrics=False):
     """temp_exp_main.py:410-544 over a device-resident sampled test pack (preprocess.EventBuffers, the
     reference's test_pack / test_edge) and the test events (device tensors); returns the epoch's figures
     (identical on every rank).  ``args``: test_bs, if_bern, beta, prior_p, test_threshold, base_type,
-    n_degree, ratios (the reference's argparse names)."""
+    n_degree, ratios (the reference's argparse names).  ``device_metrics``: every batch's row stays on the
+    device (``eval_batch(device_metrics=True)``) and the epoch makes one device-to-host copy."""
     base_model.eval()
     explainer.eval()
     num_instance = int(src.shape[0]) - 1
@@ -179,7 +225,8 @@ def eval_one_epoch(args, base_model, explainer, buf, src, dst, ts, e_idx, *, ran
         if seed is not None:
             torch.manual_seed(int(seed) + int(k))
         rows_idx = torch.arange(s, e, dtype=torch.int64, device=dev)
-        return eval_batch(args, base_model, explainer, batch_from_pack(buf, src, dst, ts, e_idx, rows_idx))
+        return eval_batch(args, base_model, explainer, batch_from_pack(buf, src, dst, ts, e_idx, rows_idx),
+                          device_metrics=device_metrics)
     gdev = dev if (world > 1 and dist.get_backend(group) == "nccl") else None
     if seed is None:
         return run_sharded(spans, one, rank, world, group, gdev)

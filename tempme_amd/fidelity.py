@@ -9,7 +9,9 @@ predictions (AP, AUC, accuracy, fidelity of probabilities and logits), then aver
 Here the masks of all ratios come from one launch of ``mask_least_kernel`` (tm_mask_least_important,
 which reproduces the CPU top-k's tie order), and all ratios go through ONE batched contrast
 (``TGN.node_embeddings(..., n_segments=len(ratios))``) instead of one call per ratio.  AP and AUC
-are computed with scikit-learn on the host, as the reference does, from the 2B predictions per ratio.
+are computed with scikit-learn on the host, as the reference does, from the 2B predictions per ratio; with
+``device_metrics=True`` all ratios' score vectors go through one ``metrics.rank_metrics`` launch instead and the
+five figures come back as a device tensor, with no copy to the host.
 """
 import math
 
@@ -114,8 +116,10 @@ def masked_contrast_tgat(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fa
 
 
 def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, e_l_cut,
-                   pos_out_ori, neg_out_ori, y_ori, subgraph_src, subgraph_tgt, subgraph_bgd):
-    """temp_exp_main.py:153-272 -> (aps_AUC, auc_AUC, acc_AUC, fid_prob_AUC, fid_logit_AUC)."""
+                   pos_out_ori, neg_out_ori, y_ori, subgraph_src, subgraph_tgt, subgraph_bgd, device_metrics=False):
+    """temp_exp_main.py:153-272 -> (aps_AUC, auc_AUC, acc_AUC, fid_prob_AUC, fid_logit_AUC): five floats, or with
+    ``device_metrics`` a float64 device tensor [5] (AP and AUC of every ratio from one rank_metrics launch against
+    the shared y_ori, the means over ratios taken on the device; nothing waits for the device)."""
     fns = {"tgn": masked_contrast, "graphmixer": masked_contrast_graphmixer, "tgat": masked_contrast_tgat}
     if args.base_type not in fns:
         raise NotImplementedError(f"threshold_test for base_type {args.base_type!r}: tgn, graphmixer and tgat "
@@ -131,6 +135,10 @@ def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fa
         pred_label = torch.where(y_pred > 0.5, 1., 0.)
         y = y_ori.reshape(1, -1).to(pos.device, torch.float32)
         acc = (pred_label == y).float().mean(1)
+        if device_metrics:
+            from .metrics import rank_metrics
+            m = rank_metrics(y.reshape(-1), y_pred).mean(0)
+            return torch.cat([m, torch.stack([acc.mean(), fid_prob.mean(), fid_logit.mean()]).double()])
         y_pred_h, y_h = y_pred.cpu().numpy(), y_ori.reshape(-1).cpu().numpy()
     aps = [average_precision_score(y_h, p) for p in y_pred_h]
     auc = [roc_auc_score(y_h, p) for p in y_pred_h]

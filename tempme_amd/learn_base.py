@@ -168,11 +168,34 @@ def _metrics(pos, neg):
     return ((score > 0.5) == true).mean(), average_precision_score(true, score), roc_auc_score(true, score)
 
 
+def _metrics_device(outs):
+    """``_metrics`` of every (pos, neg) pair as one float64 [steps, 3] array (acc, ap, auc), computed on the
+    device: the pairs of one batch size are stacked into [steps, 2B] scores against the labels [1...1, 0...0]
+    and go through one ``metrics.rank_metrics`` launch (a shorter last batch gets its own); one copy to the host
+    at the end."""
+    from .metrics import rank_metrics
+    if not outs:
+        return np.zeros((0, 3))
+    groups = {}
+    for k, (pos, neg) in enumerate(outs):
+        score = torch.cat([pos.detach().sigmoid().reshape(-1), neg.detach().sigmoid().reshape(-1)])
+        groups.setdefault(int(score.numel()), []).append((k, score))
+    res = torch.empty((len(outs), 3), dtype=torch.float64, device=outs[0][0].device)
+    for n2, members in groups.items():
+        score = torch.stack([s for _, s in members])
+        true = torch.cat([torch.ones(n2 // 2, device=score.device), torch.zeros(n2 - n2 // 2, device=score.device)])
+        acc = ((score > 0.5) == (true > 0.5)).sum(1, dtype=torch.float64) / n2
+        rows = torch.tensor([k for k, _ in members], dtype=torch.int64).to(score.device, non_blocking=True)
+        res[rows] = torch.cat([acc.reshape(-1, 1), rank_metrics(true, score)], dim=1)
+    return res.cpu().numpy()
+
+
 def train_epoch(base_model, optimizer, finder, sampler, src, dst, ts, e_idx, bs, *, idx_list=None, max_steps=None,
-                event_base=0, metrics=True):
+                event_base=0, metrics=True, device_metrics=False):
     """learn_base.py:201-253: one pass over the training edges in the order of idx_list (default: a fresh
     np.random shuffle, as the reference).  Returns {"loss": [...], "acc", "ap", "auc"}; the per-step losses
-    are read back once, at the end of the epoch."""
+    are read back once, at the end of the epoch.  ``device_metrics``: acc / ap / auc of every step from the
+    device (``_metrics_device``) instead of scikit-learn on the host."""
     base_model.train()
     base_model.set_neighbor_sampler(finder)
     num_instance = len(src)
@@ -195,13 +218,15 @@ def train_epoch(base_model, optimizer, finder, sampler, src, dst, ts, e_idx, bs,
             outs.append((pos, neg))
     out = {"loss": [float(x) for x in torch.stack(losses).cpu()] if losses else []}
     if metrics and outs:
-        m = np.array([_metrics(p, n) for p, n in outs])
+        m = _metrics_device(outs) if device_metrics else np.array([_metrics(p, n) for p, n in outs])
         out["acc"], out["ap"], out["auc"] = m.mean(axis=0)
     return out
 
 
 def eval_one_epoch(args, base_model, sampler, src, dst, ts, label, val_e_idx_l=None):
-    """learn_base.py:43-73 -> (acc, ap, None, auc), means over the batches."""
+    """learn_base.py:43-73 -> (acc, ap, None, auc), means over the batches (``args.device_metrics``: the
+    batches' figures from ``_metrics_device`` at the end of the epoch)."""
+    device_metrics = bool(getattr(args, "device_metrics", False))
     res = []
     with torch.no_grad():
         base_model = base_model.eval()
@@ -216,8 +241,8 @@ def eval_one_epoch(args, base_model, sampler, src, dst, ts, label, val_e_idx_l=N
             batch = make_batch(base_model, sampler, src[s_idx:e_idx], dst[s_idx:e_idx], ts[s_idx:e_idx], e_l_cut,
                                event_ids=s_idx + np.arange(e_idx - s_idx))
             pos, neg = _contrast(base_model, batch)
-            res.append(_metrics(pos, neg))
-    acc, ap, auc = np.array(res).mean(axis=0)
+            res.append((pos, neg) if device_metrics else _metrics(pos, neg))
+    acc, ap, auc = (_metrics_device(res) if device_metrics else np.array(res)).mean(axis=0)
     return acc, ap, None, auc
 
 
@@ -240,6 +265,8 @@ def parser():
     p.add_argument("--data_dir", type=str, default="processed")
     p.add_argument("--out_dir", type=str, default=os.path.join("params", "tgnn"))
     p.add_argument("--seed", type=int, default=0, help="seed of the keyed neighbour / negative draws")
+    p.add_argument("--device_metrics", action="store_true",
+                   help="acc / AP / AUC of every batch on the device (tm_rank_metrics) instead of scikit-learn")
     return p
 
 
@@ -289,7 +316,7 @@ def main(argv=None):
         print("start {} epoch".format(epoch))
         tr = train_epoch(base_model, optimizer, sp.train_ngh_finder, sp.train_rand_sampler, sp.train_src_l,
                          sp.train_dst_l, sp.train_ts_l, sp.train_e_idx_l, args.bs, idx_list=idx_list,
-                         event_base=epoch * num_instance)
+                         event_base=epoch * num_instance, device_metrics=args.device_metrics)
         print("train acc: {}, train ap: {}, train auc:{}, loss: {}".format(tr.get("acc"), tr.get("ap"), tr.get("auc"),
                                                                           np.mean(tr["loss"])))
         base_model.set_neighbor_sampler(sp.full_ngh_finder)

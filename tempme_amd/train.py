@@ -414,8 +414,36 @@ class GraphedTrainStep:
         return self.out
 
 
-def step_metrics(out):
-    """The per-batch training metrics of temp_exp_main.py:633-649 (host side, like the reference)."""
+def steps_metrics_device(outs):
+    """``step_metrics`` of a list of step outputs on the device: the same figures as 0-dim float64 device
+    tensors, built from the same fp32 tensors, AP and AUC from one ``metrics.rank_metrics`` launch over the stacked
+    steps (one launch per batch size: an epoch's shorter last batch gets its own).  Nothing waits for the device."""
+    from .metrics import rank_metrics
+    res = [None] * len(outs)
+    groups = {}
+    for k, out in enumerate(outs):
+        pos, neg = out["pos_logit"], out["neg_logit"]
+        po, no = out["pos_out_ori"], out["neg_out_ori"]
+        y_pred = torch.cat([pos, neg], dim=0).sigmoid()
+        pred_label = torch.where(y_pred > 0.5, 1., 0.).view(y_pred.size(0), 1)
+        fid_prob = torch.cat([pos.sigmoid() - po.sigmoid(), no.sigmoid() - neg.sigmoid()], dim=0).mean(0)
+        fid_logit = torch.cat([pos - po, no - neg], dim=0).mean(0)
+        d = lambda x: x.detach().reshape(()).double()  # noqa: E731
+        res[k] = dict(acc=d((pred_label == out["y_ori"]).float().mean()), fid_prob=d(fid_prob), fid_logit=d(fid_logit),
+                      loss=d(out["loss"]), pred_loss=d(out["pred_loss"]), kl_loss=d(out["kl_loss"]))
+        groups.setdefault(int(y_pred.numel()), []).append((k, y_pred.detach().reshape(-1), out["y_ori"].reshape(-1)))
+    for members in groups.values():
+        m = rank_metrics(torch.stack([y for _, _, y in members]), torch.stack([p for _, p, _ in members]))
+        for j, (k, _, _) in enumerate(members):
+            res[k] = dict(aps=m[j, 0], auc=m[j, 1], **res[k])
+    return res
+
+
+def step_metrics(out, device=False):
+    """The per-batch training metrics of temp_exp_main.py:633-649 (host side, like the reference; ``device``:
+    ``steps_metrics_device`` of this one step)."""
+    if device:
+        return steps_metrics_device([out])[0]
     from sklearn.metrics import average_precision_score, roc_auc_score
     pos, neg = out["pos_logit"], out["neg_logit"]
     po, no = out["pos_out_ori"], out["neg_out_ori"]
@@ -442,14 +470,18 @@ def epoch_spans(num_instance, bs, rank=0, world=1):
 
 
 def train_epoch(explainer, base_model, optimizer, buf, src, dst, ts, e_idx, bs, *, generator=None, beta=0.5,
-                prior_p=0.3, if_bern=True, grad_sync=None, rank=0, world=1, metrics=False):
+                prior_p=0.3, if_bern=True, grad_sync=None, rank=0, world=1, metrics=False, device_metrics=False):
     """One epoch over a sampled pack (temp_exp_main.py:570-632): shuffled batch order; with world > 1
     whole batches are dealt round-robin (batch b -> rank b % world) and the tail that does not fill a
-    round is dropped, so every rank takes the same number of all-reduced steps.  Returns per-step outputs."""
+    round is dropped, so every rank takes the same number of all-reduced steps.  Returns per-step outputs
+    (``metrics``: per-step ``step_metrics``; with ``device_metrics`` as device tensors, AP and AUC of the whole
+    epoch from one launch)."""
     num_instance = int(src.shape[0]) - 1              # the reference leaves the last event out (:560-561)
     perm = torch.randperm(num_instance, generator=generator).to(src.device)
     explainer.train()
     batches = _LazyBatches(buf, src, dst, ts, e_idx, perm, epoch_spans(num_instance, bs, rank, world))
     outs = run_steps(explainer, base_model, optimizer, batches, grad_sync=grad_sync, beta=beta, prior_p=prior_p,
                      if_bern=if_bern)
+    if metrics and device_metrics:
+        return steps_metrics_device(outs)
     return [step_metrics(o) for o in outs] if metrics else outs

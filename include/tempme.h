@@ -606,29 +606,35 @@ int tm_edge_importance_tab(const float *gf, int32_t n_ids, int32_t n_groups, int
  * embedding_module.py:74-75 and :211-212), else m = r.
  * The caller supplies qf[r,h] = (W_k,h^T W_q,h) query[r] and applies (fc W_v,h) to z: the
  * per-neighbour key/value projections of the reference fold into one per-row projection on each
- * side (same result up to fp32 reassociation; DESIGN.md "TGN contrast"). */
+ * side (same result up to fp32 reassociation; DESIGN.md "TGN contrast").
+ * The descriptor, tm_attn, is shared with the base TGAT (below), whose attention pass is the same computation
+ * but for the rounding of the time feature; one set of kernels serves both. */
 typedef struct {
     int32_t rows, n_ngh, n_head;
-    int32_t d_node, d_edge, d_time;       /* d_key = d_node + d_edge + d_time <= 576 (training pair: 512) */
+    int32_t d_node, d_edge, d_time;       /* d_key = d_node + d_edge + d_time <= 576 (TGN training pair: 512) */
     int32_t node_rows, edge_rows;         /* table sizes when gathered (index checks) */
     int32_t head_major_rows;              /* 1 = the reference's row pairing (see above) */
     int32_t seg_rows;                     /* > 0: rows are independent batches of seg_rows rows and the
                                              pairing runs inside each (m = base + ((r-base)*n_head+h) % seg) */
-    float temperature;                    /* sqrt(d_key), embedding_module.py:51 */
+    float temperature;                    /* TGN: sqrt(d_key), embedding_module.py:51; TGAT: sqrt(d_key / n_head) */
     const float *node_tab;                /* node_idx != NULL: [node_rows, d_node] table; else dense [rows*n_ngh, d_node] */
     const int32_t *node_idx;              /* [rows*n_ngh] or NULL */
     const float *edge_tab;                /* edge_idx != NULL: [edge_rows, d_edge] table; else dense [rows*n_ngh, d_edge] */
     const int32_t *edge_idx;              /* [rows*n_ngh] or NULL */
     const float *dt;                      /* [rows*n_ngh] time deltas (f32, as the reference casts them) */
-    const float *time_w, *time_b;         /* [d_time] TimeEncode Linear(1, d) weight and bias */
+    const float *time_w, *time_b;         /* [d_time] TimeEncode: TGN's Linear(1, d) weight and bias, TGAT's
+                                             basis_freq and phase */
     const int32_t *mask_node;             /* [rows*n_ngh]; 0 = padding (masked) */
     const float *ew;                      /* [rows*n_ngh] explanation weights or NULL (= 1) */
     const float *qf;                      /* [rows, n_head*d_key] folded queries */
     int32_t *err_flag;                    /* nullable device flag: set to TM_E_ARG on an out-of-range index */
-} tm_tgn_attn;
+} tm_attn;
+typedef tm_attn tm_tgn_attn;
+typedef tm_attn tm_tgat_attn;
 
 /* forward: z [rows, n_head*d_key], stats [rows, n_head, 2] (softmax max and sum, for the backward).
- * Limits of the pair: n_head <= 4, d_key <= 576 (nine key registers per lane), else TM_E_UNSUPPORTED. */
+ * Limits of the pair: d_key <= 576 (nine key registers per lane), else TM_E_UNSUPPORTED; n_head <= 4 (this pair
+ * reports more heads as TM_E_ARG, every other attention entry point as TM_E_UNSUPPORTED). */
 int tm_tgn_attn_fwd(const tm_tgn_attn *a, float *z, float *stats, void *stream);
 /* backward given gz = dL/dz: d_ew_parts [rows*n_head, n_ngh] holds the contribution of pair
  * q = r*n_head + h to d ew[m(q), j] (the caller sums the n_head contributions of each row);
@@ -681,35 +687,15 @@ int tm_tgn_rows_reduce(const float *grad, int64_t n_rows, int32_t d, const int64
 /* ---------------------------------------------------------------- TGAT base model (consumer of the path)
  * One attention pass of the base TGAT (TGAT/TGAT.py: forward_msg_layer :678-706 -> AttnModel :362-386 ->
  * MultiHeadAttention :110-137 -> ScaledDotProductAttention :64-80), the part that touches every
- * neighbour, in the folded form of tm_tgn_attn: per source row r and head h
- *     s_j = (qf[r,h] . key[r,j]) / temperature,   s_j = -1e10 where mask_node[m,j] == 0
- *     z[r,h] = sum_j softmax(s)_j * ew[m,j] * key[r,j]
- * with key[r,j] = [node (d_node) | edge (d_edge) | cos(fl(fl(dt[r,j]*time_w) + time_b)) (d_time)]: TGAT's
- * TimeEncode (:230-241) multiplies and then adds in place, two fp32 roundings, where TGN's Linear rounds
- * once.  m = base + ((r-base)*n_head + h) % seg with seg = seg_rows (or rows), the .repeat(n_head,1,1)
- * pairing of :128-130 inside the rows of one forward_msg call; m = r when head_major_rows is 0.
+ * neighbour: the computation of the TGN section on the same descriptor (tm_tgat_attn = tm_attn), with these
+ * differences.  The time feature is cos(fl(fl(dt[r,j]*time_w) + time_b)): TGAT's TimeEncode (:230-241)
+ * multiplies and then adds in place, two fp32 roundings, where TGN's Linear rounds once.  The head-major
+ * pairing is the .repeat(n_head,1,1) of :128-130 inside the rows of one forward_msg call (seg_rows).
  * qf[r,h] = (W_k,h^T W_q,h) query[r] with query = [src | 0 | src_t]; d_key = d_node + d_edge + d_time is
- * the model width (each head projects it to d_key / n_head), temperature = sqrt(d_key / n_head).
+ * the model width (each head projects it to d_key / n_head), so temperature = sqrt(d_key / n_head).  The
+ * backward can return d_qf.
  * Limits: n_head <= 4, d_key <= 576 (else TM_E_UNSUPPORTED).  Out-of-range node / edge ids set *err_flag
- * and read row 0.  Field meanings as in tm_tgn_attn. */
-typedef struct {
-    int32_t rows, n_ngh, n_head;
-    int32_t d_node, d_edge, d_time;
-    int32_t node_rows, edge_rows;
-    int32_t head_major_rows;
-    int32_t seg_rows;
-    float temperature;
-    const float *node_tab;                /* node_idx != NULL: [node_rows, d_node] table; else dense [rows*n_ngh, d_node] */
-    const int32_t *node_idx;              /* [rows*n_ngh] or NULL */
-    const float *edge_tab;                /* edge_idx != NULL: [edge_rows, d_edge] table; else dense [rows*n_ngh, d_edge] */
-    const int32_t *edge_idx;              /* [rows*n_ngh] or NULL */
-    const float *dt;                      /* [rows*n_ngh] time deltas (f32) */
-    const float *time_w, *time_b;         /* [d_time] TimeEncode basis_freq and phase */
-    const int32_t *mask_node;             /* [rows*n_ngh]; 0 = padding (masked) */
-    const float *ew;                      /* [rows*n_ngh] explanation weights or NULL (= 1) */
-    const float *qf;                      /* [rows, n_head*d_key] folded queries */
-    int32_t *err_flag;                    /* nullable device flag: set to TM_E_ARG on an out-of-range index */
-} tm_tgat_attn;
+ * and read row 0. */
 
 /* forward: z [rows, n_head*d_key], stats [rows, n_head, 2] (softmax max and sum, for the backward) */
 int tm_tgat_attn_fwd(const tm_tgat_attn *a, float *z, float *stats, void *stream);

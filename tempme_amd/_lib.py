@@ -54,8 +54,8 @@ class TmRng(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("split", C.c_uint32), ("side", C.c_uint32)]
 
 
-class TgnAttn(C.Structure):
-    """tm_tgn_attn (include/tempme.h)."""
+class Attn(C.Structure):
+    """tm_attn (include/tempme.h): the attention descriptor of TGN and TGAT (tm_tgn_attn, tm_tgat_attn)."""
     _fields_ = [("rows", C.c_int32), ("n_ngh", C.c_int32), ("n_head", C.c_int32),
                 ("d_node", C.c_int32), ("d_edge", C.c_int32), ("d_time", C.c_int32),
                 ("node_rows", C.c_int32), ("edge_rows", C.c_int32), ("head_major_rows", C.c_int32),
@@ -66,9 +66,7 @@ class TgnAttn(C.Structure):
                 ("mask_node", C.c_void_p), ("ew", C.c_void_p), ("qf", C.c_void_p), ("err_flag", C.c_void_p)]
 
 
-class TgatAttn(C.Structure):
-    """tm_tgat_attn (include/tempme.h): the layout of tm_tgn_attn."""
-    _fields_ = list(TgnAttn._fields_)
+TgnAttn = TgatAttn = Attn
 
 
 class TgatMerge(C.Structure):
@@ -228,21 +226,21 @@ def _sig(L):
     L.tm_edge_importance_gf.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tm_edge_importance_gf3.argtypes = [i32, i32, i32] + [vp] * 24
     L.tm_edge_importance_gf3_bern.argtypes = [i32, i32, i32] + [vp] * 26
-    L.tm_tgn_attn_fwd.argtypes = [C.POINTER(TgnAttn), vp, vp, vp]
-    L.tm_tgn_attn_bwd.argtypes = [C.POINTER(TgnAttn), vp, vp, vp, vp, vp]
+    L.tm_tgn_attn_fwd.argtypes = [C.POINTER(Attn), vp, vp, vp]
+    L.tm_tgn_attn_bwd.argtypes = [C.POINTER(Attn), vp, vp, vp, vp, vp]
     L.tm_tgn_attn_train_workspace_bytes.restype = i64
     L.tm_tgn_attn_train_workspace_bytes.argtypes = [i64, i32]
-    L.tm_tgn_attn_train_fwd.argtypes = [C.POINTER(TgnAttn), vp, C.c_float, vp, vp, vp]
-    L.tm_tgn_attn_train_bwd.argtypes = [C.POINTER(TgnAttn), vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tm_tgn_attn_train_dtab.argtypes = [C.POINTER(TgnAttn), vp, vp, vp, i64, vp, i32, vp, vp]
+    L.tm_tgn_attn_train_fwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp]
+    L.tm_tgn_attn_train_bwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tm_tgn_attn_train_dtab.argtypes = [C.POINTER(Attn), vp, vp, vp, i64, vp, i32, vp, vp]
     L.tm_tgn_rows_reduce.argtypes = [vp, i64, i32, vp, i64, vp, i32, i32, vp, vp, vp]
-    L.tm_tgat_attn_fwd.argtypes = [C.POINTER(TgatAttn), vp, vp, vp]
-    L.tm_tgat_attn_bwd.argtypes = [C.POINTER(TgatAttn), vp, vp, vp, vp, vp, vp]
+    L.tm_tgat_attn_fwd.argtypes = [C.POINTER(Attn), vp, vp, vp]
+    L.tm_tgat_attn_bwd.argtypes = [C.POINTER(Attn), vp, vp, vp, vp, vp, vp]
     L.tm_tgat_merge_fwd.argtypes = [C.POINTER(TgatMerge), vp, vp]
     L.tm_tgat_attn_train_workspace_bytes.restype = i64
     L.tm_tgat_attn_train_workspace_bytes.argtypes = [i64, i32]
-    L.tm_tgat_attn_train_fwd.argtypes = [C.POINTER(TgatAttn), vp, C.c_float, vp, vp, vp]
-    L.tm_tgat_attn_train_bwd.argtypes = [C.POINTER(TgatAttn), vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.tm_tgat_attn_train_fwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp]
+    L.tm_tgat_attn_train_bwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
     L.tm_mask_least_important.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
     L.tm_rank_metrics.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp]
     L.tm_profile_enable.argtypes = [C.c_int]

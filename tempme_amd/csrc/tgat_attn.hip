@@ -12,273 +12,15 @@
 //   TimeEncode :230-241           cos(t * basis_freq + phase): a multiply and then an in-place add, two
 //                                 fp32 roundings (TGN's Linear(1, d) rounds once)
 //
-// The attention kernels use the folded formulation of tgn_attn.hip: qf_h = W_k,h^T W_q,h query is
-// supplied per source row, the kernel builds every key on the fly from the tables and produces
-// z_h = sum_j softmax(s)_j ew_j key_j; (fc W_v) z follows in the tail.  One 64-lane wave per source
-// row, key element c = lane + 64 i in register i.  They differ from the TGN kernels in the time
-// feature's rounding and in the backward, which also returns the gradient of qf: TGAT's second layer
-// queries with the first layer's output, which depends on the explanation weights.
-// The kernels are a separate set on purpose: the TGN kernels keep their code and bitwise results.
-#include "tgat_common.h"
+// The attention entry points run attn_kernels.h's kernels, shared with TGN, in their TgatTime instances (the time
+// feature's two roundings): qf_h = W_k,h^T W_q,h query is supplied per source row, the kernel builds every key on
+// the fly from the tables and produces z_h = sum_j softmax(s)_j ew_j key_j; (fc W_v) z follows in the tail.  The
+// backward also returns the gradient of qf: TGAT's second layer queries with the first layer's output, which
+// depends on the explanation weights.
+#include "attn_kernels.h"
 
 namespace tmk {
 namespace tgat {
-
-// one online-softmax step of head state (m, l, acc) with key k
-template <int KPL>
-__device__ __forceinline__ void att_step(const tm_tgat_attn &a, const float q[KPL], const float k[KPL], int64_t ms,
-                                         float &m, float &l, float acc[KPL]) {
-    float p = 0.f;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) p = __builtin_fmaf(q[i], k[i], p);
-    float s = wave_sum(p) / a.temperature;
-    if (a.mask_node[ms] == 0) s = -1e10f;
-    const float e = a.ew ? a.ew[ms] : 1.f;
-    const float mn = fmaxf(m, s);
-    const float sc = expf(m - mn), w = expf(s - mn);
-    l = l * sc + w;
-    const float we = w * e;
-#pragma unroll
-    for (int i = 0; i < KPL; ++i) acc[i] = __builtin_fmaf(we, k[i], acc[i] * sc);
-    m = mn;
-}
-
-// n_ngh < ATT_WAVES: one wave per row walks all its neighbours
-template <int KPL, int HM>
-__global__ void __launch_bounds__(64 * ATT_WAVES) tgat_attn_fwd_kernel(tm_tgat_attn a, float *__restrict__ z,
-                                                                       float *__restrict__ stats) {
-    const int lane = threadIdx.x & 63;
-    const int64_t r = (int64_t)blockIdx.x * ATT_WAVES + (threadIdx.x >> 6);
-    if (r >= a.rows) return;
-    const int H = a.n_head, N = a.n_ngh, dk = a.d_node + a.d_edge + a.d_time;
-    const KeyLane<KPL> L = key_lane<KPL>(a, lane);
-    float q[HM][KPL], acc[HM][KPL], m[HM], l[HM];
-    int64_t mr[HM];
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-        m[h] = -__builtin_inff();
-        l[h] = 0.f;
-        mr[h] = h < H ? pair_row(a, r, h) : 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int c = lane + 64 * i;
-            q[h][i] = (h < H && c < dk) ? a.qf[(r * H + h) * dk + c] : 0.f;
-            acc[h][i] = 0.f;
-        }
-    }
-    for (int j = 0; j < N; ++j) {
-        float k[KPL];
-        build_key<KPL>(a, L, r * N + j, k);
-#pragma unroll
-        for (int h = 0; h < HM; ++h)
-            if (h < H) att_step<KPL>(a, q[h], k, mr[h] * N + j, m[h], l[h], acc[h]);
-    }
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-        if (h < H) {
-            const float inv = 1.f / l[h];
-#pragma unroll
-            for (int i = 0; i < KPL; ++i) {
-                const int c = lane + 64 * i;
-                if (c < dk) z[(r * H + h) * dk + c] = acc[h][i] * inv;
-            }
-            if (lane == 0) {
-                stats[(r * H + h) * 2] = m[h];
-                stats[(r * H + h) * 2 + 1] = l[h];
-            }
-        }
-    }
-}
-
-// n_ngh >= ATT_WAVES: one row per workgroup, wave w takes neighbours j = w, w + 4, ... with its own
-// online softmax; the partial states merge through LDS in wave order (as tgn_attn_fwd_split_kernel)
-template <int KPL, int HM>
-__global__ void __launch_bounds__(64 * ATT_WAVES) tgat_attn_fwd_split_kernel(tm_tgat_attn a, float *__restrict__ z,
-                                                                             float *__restrict__ stats) {
-    __shared__ float s_acc[ATT_WAVES][HM][KPL][64], s_m[ATT_WAVES][HM], s_l[ATT_WAVES][HM];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t r = blockIdx.x;
-    const int H = a.n_head, N = a.n_ngh, dk = a.d_node + a.d_edge + a.d_time;
-    const KeyLane<KPL> L = key_lane<KPL>(a, lane);
-    float q[HM][KPL], acc[HM][KPL], m[HM], l[HM];
-    int64_t mr[HM];
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-        m[h] = -__builtin_inff();
-        l[h] = 0.f;
-        mr[h] = h < H ? pair_row(a, r, h) : 0;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int c = lane + 64 * i;
-            q[h][i] = (h < H && c < dk) ? a.qf[(r * H + h) * dk + c] : 0.f;
-            acc[h][i] = 0.f;
-        }
-    }
-    for (int j = wv; j < N; j += ATT_WAVES) {
-        float k[KPL];
-        build_key<KPL>(a, L, r * N + j, k);
-#pragma unroll
-        for (int h = 0; h < HM; ++h)
-            if (h < H) att_step<KPL>(a, q[h], k, mr[h] * N + j, m[h], l[h], acc[h]);
-    }
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) s_acc[wv][h][i][lane] = acc[h][i];
-        if (lane == 0) {
-            s_m[wv][h] = m[h];
-            s_l[wv][h] = l[h];
-        }
-    }
-    __syncthreads();
-    if (wv != 0) return;
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-        if (h >= H) continue;
-        float M = s_m[0][h];
-#pragma unroll
-        for (int w = 1; w < ATT_WAVES; ++w) M = fmaxf(M, s_m[w][h]);
-        float Ls = 0.f, sc[ATT_WAVES];
-#pragma unroll
-        for (int w = 0; w < ATT_WAVES; ++w) {
-            sc[w] = s_l[w][h] > 0.f ? expf(s_m[w][h] - M) : 0.f;   // a wave with no neighbour adds nothing
-            Ls += s_l[w][h] * sc[w];
-        }
-        const float inv = 1.f / Ls;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            float v = 0.f;
-#pragma unroll
-            for (int w = 0; w < ATT_WAVES; ++w) v = __builtin_fmaf(s_acc[w][h][i][lane], sc[w], v);
-            const int c = lane + 64 * i;
-            if (c < dk) z[(r * H + h) * dk + c] = v * inv;
-        }
-        if (lane == 0) {
-            stats[(r * H + h) * 2] = M;
-            stats[(r * H + h) * 2 + 1] = Ls;
-        }
-    }
-}
-
-// Backward of z[r,h] = sum_j p_j e_j k_j, p = softmax(s), s_j = qf_h.k_j / T (masked: constant):
-//   c_j = gz_h.k_j;  d e_j += p_j c_j;  S_h = sum_j p_j e_j c_j;  ds_j = p_j (e_j c_j - S_h) (0 if masked)
-//   d k_j  = sum_h p_j e_j gz_h + (ds_j / T) qf_h          (node-feature columns only are written)
-//   d qf_h = (1/T) sum_j ds_j k_j                          (s_j = qf_h.k_j / T, so ds_j/dqf_h = k_j / T)
-// Pass 1 builds every key (scores and c_j) and leaves the per-(j,h) scalars in LDS.  S_h is complete only
-// after it, so pass 2 forms ds_j from those scalars: d k_j needs no key, d qf_h rebuilds key j once more
-// (the row's keys are cache-resident from pass 1) and accumulates it with the head's ds_j.
-template <int KPL, bool DNODE, bool DQF, int HM>
-__global__ void __launch_bounds__(64 * ATT_WAVES) tgat_attn_bwd_kernel(tm_tgat_attn a, const float *__restrict__ stats,
-                                                                       const float *__restrict__ gz,
-                                                                       float *__restrict__ d_parts,
-                                                                       float *__restrict__ d_node,
-                                                                       float *__restrict__ d_qf) {
-    extern __shared__ float sh[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t r = (int64_t)blockIdx.x * ATT_WAVES + wave;
-    if (r >= a.rows) return;
-    const int H = a.n_head, N = a.n_ngh, dk = a.d_node + a.d_edge + a.d_time;
-    float *pe_s = sh + (size_t)wave * 3 * N * HM;  // [N][HM] p*e
-    float *ds_s = pe_s + N * HM;                   // [N][HM] p (0 if masked)
-    float *ec_s = ds_s + N * HM;                   // [N][HM] e*c
-    const KeyLane<KPL> L = key_lane<KPL>(a, lane);
-    float q[HM][KPL], g[HM][KPL], m[HM], il[HM], S[HM];
-    int64_t mr[HM];
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-        S[h] = 0.f;
-        mr[h] = h < H ? pair_row(a, r, h) : 0;
-        m[h] = h < H ? stats[(r * H + h) * 2] : 0.f;
-        il[h] = h < H ? 1.f / stats[(r * H + h) * 2 + 1] : 0.f;
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) {
-            const int c = lane + 64 * i;
-            const bool ok = h < H && c < dk;
-            q[h][i] = ok ? a.qf[(r * H + h) * dk + c] : 0.f;
-            g[h][i] = ok ? gz[(r * H + h) * dk + c] : 0.f;
-        }
-    }
-    for (int j = 0; j < N; ++j) {
-        float k[KPL];
-        build_key<KPL>(a, L, r * N + j, k);
-#pragma unroll
-        for (int h = 0; h < HM; ++h) {
-            if (h < H) {
-                float ps = 0.f, pc = 0.f;
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) {
-                    ps = __builtin_fmaf(q[h][i], k[i], ps);
-                    pc = __builtin_fmaf(g[h][i], k[i], pc);
-                }
-                float s = wave_sum(ps) / a.temperature;
-                const float c = wave_sum(pc);
-                const int64_t ms = mr[h] * N + j;
-                const bool masked = a.mask_node[ms] == 0;
-                if (masked) s = -1e10f;
-                const float e = a.ew ? a.ew[ms] : 1.f;
-                const float p = expf(s - m[h]) * il[h];
-                S[h] = __builtin_fmaf(p * e, c, S[h]);
-                if (lane == 0) {
-                    d_parts[(r * H + h) * N + j] = p * c;
-                    if (DNODE || DQF) {
-                        pe_s[j * HM + h] = p * e;
-                        ds_s[j * HM + h] = masked ? 0.f : p;
-                        ec_s[j * HM + h] = e * c;
-                    }
-                }
-            }
-        }
-    }
-    if (!DNODE && !DQF) return;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const float invT = 1.f / a.temperature;
-    float dq[HM][KPL];
-#pragma unroll
-    for (int h = 0; h < HM; ++h)
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) dq[h][i] = 0.f;
-    for (int j = 0; j < N; ++j) {
-        float dkv[KPL], k[KPL];
-#pragma unroll
-        for (int i = 0; i < KPL; ++i) dkv[i] = 0.f;
-        if (DQF) build_key<KPL>(a, L, r * N + j, k);
-#pragma unroll
-        for (int h = 0; h < HM; ++h) {
-            if (h < H) {
-                const float pe = pe_s[j * HM + h];
-                const float ds = ds_s[j * HM + h] * (ec_s[j * HM + h] - S[h]) * invT;
-                if (DNODE) {
-#pragma unroll
-                    for (int i = 0; i < KPL; ++i)
-                        dkv[i] = __builtin_fmaf(pe, g[h][i], __builtin_fmaf(ds, q[h][i], dkv[i]));
-                }
-                if (DQF) {
-#pragma unroll
-                    for (int i = 0; i < KPL; ++i) dq[h][i] = __builtin_fmaf(ds, k[i], dq[h][i]);
-                }
-            }
-        }
-        if (DNODE) {
-            float *dst = d_node + (r * N + j) * (int64_t)a.d_node;
-#pragma unroll
-            for (int i = 0; i < KPL; ++i)
-                if (L.seg[i] == 0) dst[L.off[i]] = dkv[i];
-        }
-    }
-    if (DQF) {
-#pragma unroll
-        for (int h = 0; h < HM; ++h) {
-            if (h < H) {
-#pragma unroll
-                for (int i = 0; i < KPL; ++i) {
-                    const int c = lane + 64 * i;
-                    if (c < dk) d_qf[(r * H + h) * dk + c] = dq[h][i];
-                }
-            }
-        }
-    }
-}
 
 // ------------------------------------------------------------------ fused layer tail
 // Per tile of MG_ROWS source rows (one workgroup, all d_key columns, so the LayerNorm reduction stays in LDS):
@@ -448,104 +190,17 @@ static size_t mg_lds_bytes(int dk, int F) {
 }  // namespace tmk
 
 using namespace tmk;
+using namespace tmk::attn;
 using namespace tmk::tgat;
 
-static int check_attn(const tm_tgat_attn *a, const char *who) {
-    if (!a) return fail(TM_E_ARG, std::string(who) + ": NULL descriptor");
-    if (a->rows < 0 || a->n_ngh <= 0 || a->n_head < 1 || a->d_node <= 0 || a->d_edge < 0 || a->d_time < 0 ||
-        !(a->temperature > 0.f))
-        return fail(TM_E_ARG, std::string(who) + ": bad sizes");
-    if (a->n_head > ATT_MAXH) return fail(TM_E_UNSUPPORTED, std::string(who) + ": n_head > 4");
-    const int dk = a->d_node + a->d_edge + a->d_time;
-    if (dk > 64 * 9) return fail(TM_E_UNSUPPORTED, std::string(who) + ": d_key > 576");
-    if (a->rows == 0) return TM_OK;
-    if (!a->node_tab || (a->d_edge && !a->edge_tab) || !a->dt || (a->d_time && (!a->time_w || !a->time_b)) ||
-        !a->mask_node || !a->qf)
-        return fail(TM_E_ARG, std::string(who) + ": NULL pointer");
-    if (a->seg_rows < 0 || (a->seg_rows > 0 && a->rows % a->seg_rows))
-        return fail(TM_E_SHAPE, std::string(who) + ": rows must be a multiple of seg_rows");
-    if ((a->node_idx && a->node_rows <= 0) || (a->edge_idx && a->edge_rows <= 0))
-        return fail(TM_E_ARG, std::string(who) + ": empty feature table");
-    return TM_OK;
-}
-
-template <int KPL>
-static void launch_fwd(const tm_tgat_attn &a, float *z, float *stats, hipStream_t s) {
-    // the heads' register arrays are sized for 2 heads where that covers them, else for 4 (as the TGN kernels)
-    if (a.n_ngh >= ATT_WAVES) {
-        if (a.n_head <= 2) tgat_attn_fwd_split_kernel<KPL, 2><<<dim3((unsigned)a.rows), 64 * ATT_WAVES, 0, s>>>(a, z, stats);
-        else tgat_attn_fwd_split_kernel<KPL, ATT_MAXH><<<dim3((unsigned)a.rows), 64 * ATT_WAVES, 0, s>>>(a, z, stats);
-        return;
-    }
-    const unsigned blocks = (unsigned)((a.rows + ATT_WAVES - 1) / ATT_WAVES);
-    if (a.n_head <= 2) tgat_attn_fwd_kernel<KPL, 2><<<dim3(blocks), 64 * ATT_WAVES, 0, s>>>(a, z, stats);
-    else tgat_attn_fwd_kernel<KPL, ATT_MAXH><<<dim3(blocks), 64 * ATT_WAVES, 0, s>>>(a, z, stats);
-}
-
-template <int KPL, int HM>
-static void launch_bwd_h(const tm_tgat_attn &a, const float *stats, const float *gz, float *dp, float *dn, float *dq,
-                         hipStream_t s) {
-    const unsigned blocks = (unsigned)((a.rows + ATT_WAVES - 1) / ATT_WAVES);
-    const size_t lds = (dn || dq) ? sizeof(float) * 3 * a.n_ngh * HM * ATT_WAVES : 0;
-    const dim3 g(blocks), b(64 * ATT_WAVES);
-    if (dn && dq) tgat_attn_bwd_kernel<KPL, true, true, HM><<<g, b, lds, s>>>(a, stats, gz, dp, dn, dq);
-    else if (dn) tgat_attn_bwd_kernel<KPL, true, false, HM><<<g, b, lds, s>>>(a, stats, gz, dp, dn, dq);
-    else if (dq) tgat_attn_bwd_kernel<KPL, false, true, HM><<<g, b, lds, s>>>(a, stats, gz, dp, dn, dq);
-    else tgat_attn_bwd_kernel<KPL, false, false, HM><<<g, b, 0, s>>>(a, stats, gz, dp, dn, dq);
-}
-
-template <int KPL>
-static void launch_bwd(const tm_tgat_attn &a, const float *stats, const float *gz, float *dp, float *dn, float *dq,
-                       hipStream_t s) {
-    if (a.n_head <= 2) launch_bwd_h<KPL, 2>(a, stats, gz, dp, dn, dq, s);
-    else launch_bwd_h<KPL, ATT_MAXH>(a, stats, gz, dp, dn, dq, s);
-}
-
-#define TM_TGAT_KPL_DISPATCH(KPLV, CALL) \
-    switch (KPLV) {                      \
-        case 1: CALL(1); break;          \
-        case 2: CALL(2); break;          \
-        case 3: CALL(3); break;          \
-        case 4: CALL(4); break;          \
-        case 5: CALL(5); break;          \
-        case 6: CALL(6); break;          \
-        case 7: CALL(7); break;          \
-        case 8: CALL(8); break;          \
-        default: CALL(9); break;         \
-    }
-
 extern "C" int tm_tgat_attn_fwd(const tm_tgat_attn *a, float *z, float *stats, void *stream) {
-    int rc = check_attn(a, "tm_tgat_attn_fwd");
-    if (rc != TM_OK || a->rows == 0) return rc;
-    if (!z || !stats) return fail(TM_E_ARG, "tm_tgat_attn_fwd: NULL output");
-    hipStream_t s = (hipStream_t)stream;
-    const int kpl = (a->d_node + a->d_edge + a->d_time + 63) / 64;
-    hipEvent_t pe = prof_begin(s);
-#define TM_FWD(K) launch_fwd<K>(*a, z, stats, s)
-    TM_TGAT_KPL_DISPATCH(kpl, TM_FWD)
-#undef TM_FWD
-    TM_CHECK_LAUNCH();
-    prof_end("tgat_attn_fwd_kernel", s, pe);
-    return TM_OK;
+    return attn_fwd<TgatTime>(a, z, stats, stream, "tm_tgat_attn_fwd", "tgat_attn_fwd_kernel");
 }
 
 extern "C" int tm_tgat_attn_bwd(const tm_tgat_attn *a, const float *stats, const float *gz, float *d_ew_parts,
                                 float *d_node, float *d_qf, void *stream) {
-    int rc = check_attn(a, "tm_tgat_attn_bwd");
-    if (rc != TM_OK || a->rows == 0) return rc;
-    if (!stats || !gz || !d_ew_parts) return fail(TM_E_ARG, "tm_tgat_attn_bwd: NULL pointer");
-    if (d_node && a->node_idx) return fail(TM_E_ARG, "tm_tgat_attn_bwd: d_node needs a dense node table");
-    if ((size_t)3 * a->n_ngh * ATT_MAXH * ATT_WAVES * sizeof(float) > 64 * 1024)
-        return fail(TM_E_UNSUPPORTED, "tm_tgat_attn_bwd: n_ngh too large");
-    hipStream_t s = (hipStream_t)stream;
-    const int kpl = (a->d_node + a->d_edge + a->d_time + 63) / 64;
-    hipEvent_t pe = prof_begin(s);
-#define TM_BWD(K) launch_bwd<K>(*a, stats, gz, d_ew_parts, d_node, d_qf, s)
-    TM_TGAT_KPL_DISPATCH(kpl, TM_BWD)
-#undef TM_BWD
-    TM_CHECK_LAUNCH();
-    prof_end("tgat_attn_bwd_kernel", s, pe);
-    return TM_OK;
+    return attn_bwd<TgatTime, true>(a, stats, gz, d_ew_parts, d_node, d_qf, stream, "tm_tgat_attn_bwd",
+                                    "tgat_attn_bwd_kernel");
 }
 
 extern "C" int tm_tgat_merge_fwd(const tm_tgat_merge *a, float *out, void *stream) {

@@ -20,7 +20,7 @@ import torch
 from sklearn.metrics import average_precision_score, roc_auc_score
 
 from . import _lib as L
-from .tgn import _as_dev
+from .attn_op import _as_dev
 
 
 def _masked_nodes(explanation, subgraphs, N, ratios, dev, hops=2):

@@ -24,7 +24,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .tgn import MergeLayer, _as_dev
+from .attn_op import _as_dev
+from .tgn import MergeLayer
 
 
 class TimeEncoder(nn.Module):

@@ -14,7 +14,8 @@ What the reference computes per side with ``num_layers = 2`` (forward_msg :607-6
 The query of a pass is ``[src | 0 (d_edge) | src_t]`` with src_t = TimeEncode(0) for roots and
 TimeEncode(cut - t1) for the hop-1 rows of pass 2.
 
-Here every pass is one launch of ``tgat_attn_fwd_kernel`` (csrc/tgat_attn.hip) over the rows of all sides,
+Here every pass is one launch of the attention forward (csrc/attn_kernels.h, shared with TGN, in its TGAT
+instances; C ABI ``tm_tgat_attn_fwd``, autograd wrapper ``attn_op.AttnFn``) over the rows of all sides,
 the sides being segments of ``seg_rows`` = B (or B*N) rows so the reference's head-major mask / weight
 pairing stays inside one forward_msg call.  The per-neighbour projections fold into per-row ones
 (qf = W_k^T W_q query before the kernel, G = fc W_v after it, as tgn.py).  The layer tail (G z + residual,
@@ -26,11 +27,11 @@ gradient of the folded query (through h0').  On these paths the base model is fr
 
 Training the base itself (learn_base.py) is opt-in: after ``model.train_on_hip()``, ``model.train()`` calls of
 ``contrast(..., if_explain=False)`` / ``get_node_emb`` with gradients enabled run ``tm_tgat_attn_train_fwd`` /
-``tm_tgat_attn_train_bwd`` (csrc/tgat_train.hip): the attention dropout as a keep mask inside the kernels, fc's
-dropout in the torch tail, P = W_k^T W_q and G = fc W_v folded in fp32 from the live parameters under autograd (so
-d qf and d z reach w_qs, w_ks, w_vs and fc), the query-side time features as differentiable torch ops and the
-key-side time gradient from the kernel's d_time.  ``loss.backward()`` then fills .grad on all 36 trainable
-parameters.
+``tm_tgat_attn_train_bwd`` (csrc/attn_train.h, ``attn_op.TrainAttnFn``): the attention dropout as a keep mask
+inside the kernels, fc's dropout in the torch tail, P = W_k^T W_q and G = fc W_v folded in fp32 from the live
+parameters under autograd (so d qf and d z reach w_qs, w_ks, w_vs and fc), the query-side time features as
+differentiable torch ops and the key-side time gradient from the kernel's d_time.  ``loss.backward()`` then fills
+.grad on all 36 trainable parameters.
 """
 import numpy as np
 import torch
@@ -38,7 +39,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .tgn import _as_dev
+from .attn_op import AttnFn, TrainAttnFn, _as_dev
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -124,111 +125,7 @@ class AttnModel(nn.Module):
                                                     d_v=self.model_dim // n_head, dropout=drop_out)
 
 
-# ------------------------------------------------------------------ the HIP attention op
-class _TgatAttnFn(torch.autograd.Function):
-    """z = tm_tgat_attn_fwd(...); backward through tm_tgat_attn_bwd: explanation weights, the dense
-    neighbour table (pass 3's h1') and the folded query (pass 3's h0')."""
-
-    @staticmethod
-    def forward(ctx, qf, ngh_dense, ew, spec):
-        dev = qf.device
-        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
-        desc = _desc(spec, qf, ngh_dense, ew)
-        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
-        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
-        if R:
-            L.check(L.lib().tm_tgat_attn_fwd(L.C.byref(desc), L.ptr(z), L.ptr(stats), L.stream_ptr(dev)),
-                    "TGAT attention")
-        ctx.spec = spec
-        ctx.save_for_backward(qf, ngh_dense, ew, stats)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        qf, ngh_dense, ew, stats = ctx.saved_tensors
-        spec = ctx.spec
-        R, H, N = spec["rows"], spec["n_head"], spec["n_ngh"]
-        dev = gz.device
-        gz = gz.contiguous().float()
-        want_node = ngh_dense is not None and ctx.needs_input_grad[1]
-        parts = torch.empty((R * H, N), dtype=torch.float32, device=dev)
-        d_node = torch.empty_like(ngh_dense) if want_node else None
-        d_qf = torch.empty_like(qf) if ctx.needs_input_grad[0] else None
-        if R:
-            desc = _desc(spec, qf, ngh_dense, ew)
-            L.check(L.lib().tm_tgat_attn_bwd(L.C.byref(desc), L.ptr(stats), L.ptr(gz), L.ptr(parts), L.ptr(d_node),
-                                             L.ptr(d_qf), L.stream_ptr(dev)), "TGAT attention backward")
-        d_ew = None
-        if ew is not None and ctx.needs_input_grad[2]:
-            # pair q = r*H + h contributes to weight row base + ((r-base)*H + h) % seg of its segment
-            seg = spec.get("seg_rows", 0) or R
-            if spec["head_major"]:
-                d_ew = parts.view(R // seg, H, seg, N).sum(1)
-            else:
-                d_ew = parts.view(R, H, N).sum(1)
-            d_ew = d_ew.reshape(ew.shape)
-        return d_qf, d_node, d_ew, None
-
-
-class _TgatTrainAttnFn(torch.autograd.Function):
-    """z = tm_tgat_attn_train_fwd(...) with the attention dropout's keep mask; backward through
-    tm_tgat_attn_train_bwd: the folded query, the dense neighbour table (pass 3's h1') and, through the keys'
-    time features, TimeEncode's basis_freq and phase."""
-
-    @staticmethod
-    def forward(ctx, qf, ngh_dense, freq, phase, spec, keep, keep_scale):
-        dev = qf.device
-        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
-        desc = _desc(spec, qf, ngh_dense, None)
-        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
-        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
-        L.check(L.lib().tm_tgat_attn_train_fwd(L.C.byref(desc), L.ptr(keep), keep_scale, L.ptr(z), L.ptr(stats),
-                                               L.stream_ptr(dev)), "TGAT training attention")
-        ctx.spec, ctx.keep, ctx.keep_scale = spec, keep, keep_scale
-        # the backward recomputes the keys from basis_freq and phase: saved, so that an in-place change of either
-        # between forward and backward is caught by autograd's version check
-        ctx.save_for_backward(qf, ngh_dense, stats, freq, phase)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        qf, ngh_dense, stats, freq, phase = ctx.saved_tensors
-        spec = dict(ctx.spec, time_w=freq, time_b=phase)
-        R, dT = spec["rows"], spec["d_time"]
-        dev = gz.device
-        gz = gz.contiguous().float()
-        d_node = torch.empty_like(ngh_dense) if ngh_dense is not None else None
-        d_qf = torch.empty_like(qf)
-        d_time = torch.empty((2, dT), dtype=torch.float32, device=dev)
-        ws = torch.empty(int(L.lib().tm_tgat_attn_train_workspace_bytes(R, dT)), dtype=torch.uint8, device=dev)
-        desc = _desc(spec, qf, ngh_dense, None)
-        L.check(L.lib().tm_tgat_attn_train_bwd(L.C.byref(desc), L.ptr(ctx.keep), ctx.keep_scale, L.ptr(stats),
-                                               L.ptr(gz), None, L.ptr(d_node), L.ptr(d_qf), L.ptr(d_time), L.ptr(ws),
-                                               L.stream_ptr(dev)), "TGAT training attention backward")
-        return d_qf, d_node, d_time[0], d_time[1], None, None, None
-
-
-def _desc(spec, qf, ngh_dense, ew):
-    a = L.TgatAttn()
-    a.rows, a.n_ngh, a.n_head = spec["rows"], spec["n_ngh"], spec["n_head"]
-    a.d_node, a.d_edge, a.d_time = spec["d_node"], spec["d_edge"], spec["d_time"]
-    a.node_rows, a.edge_rows = spec["node_rows"], spec["edge_rows"]
-    a.head_major_rows = 1 if spec["head_major"] else 0
-    a.seg_rows = spec.get("seg_rows", 0)
-    a.temperature = spec["temperature"]
-    a.node_tab = (ngh_dense if ngh_dense is not None else spec["node_tab"]).data_ptr()
-    a.node_idx = spec["node_idx"].data_ptr() if spec["node_idx"] is not None else None
-    a.edge_tab = spec["edge_tab"].data_ptr()
-    a.edge_idx = spec["edge_idx"].data_ptr()
-    a.dt = spec["dt"].data_ptr()
-    a.time_w, a.time_b = spec["time_w"].data_ptr(), spec["time_b"].data_ptr()
-    a.mask_node = spec["mask_node"].data_ptr()
-    a.ew = ew.data_ptr() if ew is not None else None
-    a.qf = qf.data_ptr()
-    a.err_flag = spec["err"].data_ptr()
-    return a
-
-
+# ------------------------------------------------------------------ the layer tail (the attention op: attn_op.py)
 def merge_fwd(z, query, lw, feat):
     """The fused layer tail (tm_tgat_merge_fwd) on a packed attention model ``lw`` -> [rows, feat]."""
     dev = z.device
@@ -367,8 +264,8 @@ class TGAT(nn.Module):
                     node_rows=pk["tab"].shape[0], edge_rows=pk["etab"].shape[0], head_major=self.head_major_rows,
                     temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"],
                     edge_idx=edge_idx, dt=dt, time_w=pk["freq"], time_b=pk["phase"], mask_node=mask_node,
-                    err=pk["err"], seg_rows=seg)
-        z = _TgatAttnFn.apply(qf, ngh_dense, ew, spec)
+                    err=pk["err"], seg_rows=seg, flavour="tgat")
+        z = AttnFn.apply(qf, ngh_dense, ew, spec)
         if self.fused_tail and not (torch.is_grad_enabled() and (z.requires_grad or query.requires_grad)):
             return merge_fwd(z, query, lw, fd)
         return merge_torch(z, query, lw, fd)
@@ -480,8 +377,8 @@ class TGAT(nn.Module):
                     d_time=self.time_dim, node_rows=self.n_feat_th.shape[0], edge_rows=self.e_feat_th.shape[0],
                     head_major=self.head_major_rows, temperature=mh.temperature, node_tab=self.n_feat_th,
                     node_idx=node_idx, edge_tab=self.e_feat_th, edge_idx=edge_idx, dt=dt, time_w=te.basis_freq.detach(),
-                    time_b=te.phase.detach(), mask_node=mask_node, err=self._train_err, seg_rows=seg)
-        z = _TgatTrainAttnFn.apply(qf, ngh_dense, te.basis_freq, te.phase, spec, akeep, scale)
+                    time_b=te.phase.detach(), mask_node=mask_node, err=self._train_err, seg_rows=seg, flavour="tgat")
+        z = TrainAttnFn.apply(qf, ngh_dense, None, te.basis_freq, te.phase, spec, akeep, scale)
         out = torch.addmm(mh.fc.bias, z, Gt)
         if fkeep is not None:
             out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (TGAT.py:134)

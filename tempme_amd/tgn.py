@@ -9,13 +9,14 @@ constructor, submodule names (a reference ``state_dict`` loads as is), construct
 
 ``contrast`` runs on the HIP device:
   * per layer, the neighbour-facing part (key construction from the feature tables, scores for all
-    heads, masked softmax, explanation weight, weighted key sum) is one launch of
-    ``tgn_attn_fwd_kernel`` (csrc/tgn_attn.hip, C ABI ``tm_tgn_attn_fwd``);
+    heads, masked softmax, explanation weight, weighted key sum) is one launch of the attention forward
+    (``attn_fwd_kernel`` / ``attn_fwd_split_kernel`` of csrc/attn_kernels.h, shared with TGAT, in their TGN
+    instances; C ABI ``tm_tgn_attn_fwd``, autograd wrapper ``attn_op.AttnFn``);
   * the reference's per-neighbour projections fold into per-row ones: qf = (W_k^T W_q) query before
     the kernel and (fc W_v) z after it, two hipBLASLt GEMMs over source rows, followed by the
     residual LayerNorm and the merger MLP (torch ops on the device);
   * gradients with respect to the explanation weights (the explainer's training signal,
-    temp_exp_main.py:624-631) come from ``tgn_attn_bwd_kernel`` (``tm_tgn_attn_bwd``) and torch
+    temp_exp_main.py:624-631) come from ``attn_bwd_kernel`` (``tm_tgn_attn_bwd``) and torch
     autograd for the dense per-row algebra.  The base model is frozen: its parameters get no .grad.
 
 Scope: the "graph_attention" embedding module, 2-hop subgraphs.  With ``forbidden_memory_update=True`` (the path
@@ -27,12 +28,13 @@ and get_node_emb are stateful as tgn.py:123-196: they embed over the updated mem
 clear their messages and store the batch's raw messages.  The state lives on the device (``Memory.msg_raw`` /
 ``msg_ts`` / ``msg_flag``: under the ``last`` aggregator one raw message per node is all the reference reads) and
 moves on without a loop over events and without a host synchronisation.  After ``train_on_hip()`` a ``train()``
-step runs the training pair ``tm_tgn_attn_train_fwd`` / ``tm_tgn_attn_train_bwd`` (csrc/tgn_train.hip) with the
-reference's two dropouts on the live parameters, and ``loss.backward()`` fills ``.grad`` on every tensor the
-reference's step trains -- TimeEncode, the message MLP and the GRU cell (through the updated memory rows the keys
-and queries gather: ``tm_tgn_attn_train_dtab`` / ``tm_tgn_rows_reduce``, no atomics), the two attention layers and
-``affinity_score``.  ``messages_to_dict()`` / ``messages_from_dict()`` move the pending messages between the device
-store and ``memory.messages``, which the frozen path reads (it calls the former itself when the store is newer).
+step runs the training pair ``tm_tgn_attn_train_fwd`` / ``tm_tgn_attn_train_bwd`` (csrc/attn_train.h, entry
+points in csrc/tgn_train.hip; ``attn_op.TrainAttnFn``) with the reference's two dropouts on the live parameters,
+and ``loss.backward()`` fills ``.grad`` on every tensor the reference's step trains -- TimeEncode, the message MLP
+and the GRU cell (through the updated memory rows the keys and queries gather: ``tm_tgn_attn_train_dtab`` /
+``tm_tgn_rows_reduce``, no atomics), the two attention layers and ``affinity_score``.  ``messages_to_dict()`` /
+``messages_from_dict()`` move the pending messages between the device store and ``memory.messages``, which the
+frozen path reads (it calls the former itself when the store is newer).
 """
 from collections import defaultdict
 
@@ -42,6 +44,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
+from .attn_op import AttnFn, TrainAttnFn, _as_dev
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -262,49 +265,7 @@ class GraphAttentionEmbedding(nn.Module):
             for _ in range(n_layers)])
 
 
-# ------------------------------------------------------------------ the HIP attention op
-class _TgnAttnFn(torch.autograd.Function):
-    """z = tm_tgn_attn_fwd(...); backward through tm_tgn_attn_bwd (explanation weights and the dense
-    neighbour-feature rows of the upper layer)."""
-
-    @staticmethod
-    def forward(ctx, qf, ngh_dense, ew, spec):
-        dev = qf.device
-        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
-        desc = _desc(spec, qf, ngh_dense, ew)
-        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
-        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
-        if R:
-            L.check(L.lib().tm_tgn_attn_fwd(L.C.byref(desc), L.ptr(z), L.ptr(stats), L.stream_ptr(dev)),
-                    "TGN attention")
-        ctx.spec = spec
-        ctx.save_for_backward(qf, ngh_dense, ew, stats)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        qf, ngh_dense, ew, stats = ctx.saved_tensors
-        spec = ctx.spec
-        if ctx.needs_input_grad[0]:
-            raise NotImplementedError("TGN attention: gradient with respect to the queries (base model is frozen)")
-        R, H, N = spec["rows"], spec["n_head"], spec["n_ngh"]
-        dev = gz.device
-        gz = gz.contiguous().float()
-        want_node = ngh_dense is not None and ctx.needs_input_grad[1]
-        parts = torch.empty((R * H, N), dtype=torch.float32, device=dev)
-        d_node = torch.empty_like(ngh_dense) if want_node else None
-        if R:
-            desc = _desc(spec, qf, ngh_dense, ew)
-            L.check(L.lib().tm_tgn_attn_bwd(L.C.byref(desc), L.ptr(stats), L.ptr(gz), L.ptr(parts),
-                                            L.ptr(d_node), L.stream_ptr(dev)), "TGN attention backward")
-        d_ew = None
-        if ew is not None and ctx.needs_input_grad[2]:
-            # pair q = r*H + h contributes to explanation-weight row q % R (head-major) or r
-            d_ew = parts.view(H, R, N).sum(0) if spec["head_major"] else parts.view(R, H, N).sum(1)
-            d_ew = d_ew.reshape(ew.shape)
-        return None, d_node, d_ew, None
-
-
+# ------------------------------------------------------------------ the HIP attention op (attn_op.py): TGN's own parts
 def _rows_by_table_row(idx, n_rows):
     """The entries of ``idx`` grouped by the table row they name, for the reductions without atomics: a stable
     sort's permutation [len(idx)] and the segment offsets [n_rows + 1] (both int64, on idx's device; no host
@@ -337,83 +298,16 @@ class _GatherRowsFn(torch.autograd.Function):
         return out, None, None
 
 
-class _TgnTrainAttnFn(torch.autograd.Function):
-    """z = tm_tgn_attn_train_fwd(...) with the attention dropout's keep mask; backward through
-    tm_tgn_attn_train_bwd: the folded query, TimeEncode's weight and bias through the keys' time features, and
-    the keys' node features -- the dense neighbour rows of layer 1, or the rows of the gathered table of layer 0
-    (tm_tgn_attn_train_dtab; no [rows*n_ngh, d_node] tensor is formed)."""
-
-    @staticmethod
-    def forward(ctx, qf, ngh_dense, tab, tw, tb, spec, keep, keep_scale):
-        dev = qf.device
-        R, H, dk = spec["rows"], spec["n_head"], spec["d_key"]
-        spec = dict(spec, node_tab=tab, time_w=tw, time_b=tb)
-        desc = _desc(spec, qf, ngh_dense, None)
-        z = torch.empty((R, H * dk), dtype=torch.float32, device=dev)
-        stats = torch.empty((R, H, 2), dtype=torch.float32, device=dev)
-        L.check(L.lib().tm_tgn_attn_train_fwd(L.C.byref(desc), L.ptr(keep), keep_scale, L.ptr(z), L.ptr(stats),
-                                              L.stream_ptr(dev)), "TGN training attention")
-        ctx.spec, ctx.keep, ctx.keep_scale = spec, keep, keep_scale
-        ctx.dense = ngh_dense is not None
-        # the backward rebuilds the keys: saved, so that an in-place change between forward and backward is
-        # caught by autograd's version check
-        ctx.save_for_backward(qf, ngh_dense if ctx.dense else tab, stats, tw, tb)
-        return z
-
-    @staticmethod
-    def backward(ctx, gz):
-        qf, node, stats, tw, tb = ctx.saved_tensors
-        spec = dict(ctx.spec, node_tab=node, time_w=tw, time_b=tb)
-        R, N, H, dT = spec["rows"], spec["n_ngh"], spec["n_head"], spec["d_time"]
-        dev = gz.device
-        lib = L.lib()
-        gz = gz.contiguous().float()
-        want_tab = not ctx.dense and ctx.needs_input_grad[2]
-        d_node = torch.empty_like(node) if ctx.dense and ctx.needs_input_grad[1] else None
-        d_qf = torch.empty_like(qf)
-        d_time = torch.empty((2, dT), dtype=torch.float32, device=dev)
-        ab = torch.empty((R, N, H, 2), dtype=torch.float32, device=dev) if want_tab else None
-        ws = torch.empty(int(lib.tm_tgn_attn_train_workspace_bytes(R, dT)), dtype=torch.uint8, device=dev)
-        desc = _desc(spec, qf, node if ctx.dense else None, None)
-        L.check(lib.tm_tgn_attn_train_bwd(L.C.byref(desc), L.ptr(ctx.keep), ctx.keep_scale, L.ptr(stats), L.ptr(gz),
-                                          None, L.ptr(d_node), L.ptr(d_qf), L.ptr(d_time), L.ptr(ab), L.ptr(ws),
-                                          L.stream_ptr(dev)), "TGN training attention backward")
-        d_tab = None
-        if want_tab:
-            order, seg = _rows_by_table_row(spec["node_idx"], node.shape[0])
-            d_tab = torch.empty_like(node)
-            # row 0 is the padding node: a large share of the slots, and nothing trainable behind it
-            L.check(lib.tm_tgn_attn_train_dtab(L.C.byref(desc), L.ptr(ab), L.ptr(gz), L.ptr(order), order.shape[0],
-                                               L.ptr(seg), 1, L.ptr(d_tab), L.stream_ptr(dev)),
-                    "TGN gathered-table gradient")
-        return d_qf, d_node, d_tab, d_time[0], d_time[1], None, None, None
-
-
-def _desc(spec, qf, ngh_dense, ew):
-    a = L.TgnAttn()
-    a.rows, a.n_ngh, a.n_head = spec["rows"], spec["n_ngh"], spec["n_head"]
-    a.d_node, a.d_edge, a.d_time = spec["d_node"], spec["d_edge"], spec["d_time"]
-    a.node_rows, a.edge_rows = spec["node_rows"], spec["edge_rows"]
-    a.head_major_rows = 1 if spec["head_major"] else 0
-    a.seg_rows = spec.get("seg_rows", 0)
-    a.temperature = spec["temperature"]
-    a.node_tab = (ngh_dense if ngh_dense is not None else spec["node_tab"]).data_ptr()
-    a.node_idx = spec["node_idx"].data_ptr() if spec["node_idx"] is not None else None
-    a.edge_tab = spec["edge_tab"].data_ptr() if spec["edge_tab"] is not None else None
-    a.edge_idx = spec["edge_idx"].data_ptr() if spec["edge_idx"] is not None else None
-    a.dt = spec["dt"].data_ptr()
-    a.time_w, a.time_b = spec["time_w"].data_ptr(), spec["time_b"].data_ptr()
-    a.mask_node = spec["mask_node"].data_ptr()
-    a.ew = ew.data_ptr() if ew is not None else None
-    a.qf = qf.data_ptr()
-    a.err_flag = spec["err"].data_ptr()
-    return a
-
-
-def _as_dev(x, device, dtype):
-    if isinstance(x, torch.Tensor):
-        return x.to(device=device, dtype=dtype)
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(device=device, dtype=dtype)
+def _gathered_table_grad(spec, desc, slot_ab, gz, tab):
+    """TrainAttnFn's ``table_grad`` hook: the gradient of the gathered node table of layer 0 from the backward's
+    slot_ab (tm_tgn_attn_train_dtab; no [rows*n_ngh, d_node] tensor is formed)."""
+    order, seg = _rows_by_table_row(spec["node_idx"], tab.shape[0])
+    d_tab = torch.empty_like(tab)
+    # row 0 is the padding node: a large share of the slots, and nothing trainable behind it
+    L.check(L.lib().tm_tgn_attn_train_dtab(L.C.byref(desc), L.ptr(slot_ab), L.ptr(gz), L.ptr(order), order.shape[0],
+                                           L.ptr(seg), 1, L.ptr(d_tab), L.stream_ptr(gz.device)),
+            "TGN gathered-table gradient")
+    return d_tab
 
 
 def _cat_rows(xs):
@@ -723,8 +617,8 @@ class TGN(nn.Module):
                     temperature=mh.temperature, node_idx=node_idx,
                     edge_tab=edge_dense if edge_dense is not None else self.e_feat_th,
                     edge_idx=None if edge_dense is not None else edge_idx, dt=dt, mask_node=mask_node,
-                    err=self._live_err, seg_rows=seg)
-        z = _TgnTrainAttnFn.apply(qf, ngh_dense, None if ngh_dense is not None else tab, tw, tb, spec, akeep, scale)
+                    err=self._live_err, seg_rows=seg, flavour="tgn", table_grad=_gathered_table_grad)
+        z = TrainAttnFn.apply(qf, ngh_dense, None if ngh_dense is not None else tab, tw, tb, spec, akeep, scale)
         out = torch.addmm(mh.fc.bias, z, G.t())
         if fkeep is not None:
             out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (embedding_module.py:84)
@@ -909,8 +803,8 @@ class TGN(nn.Module):
                     temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx,
                     edge_tab=edge_dense if edge_dense is not None else pk["etab"],
                     edge_idx=None if edge_dense is not None else edge_idx, dt=dt, time_w=pk["tw"],
-                    time_b=pk["tb"], mask_node=mask_node, err=pk["err"], seg_rows=seg)
-        z = _TgnAttnFn.apply(qf, ngh_dense, ew, spec)
+                    time_b=pk["tb"], mask_node=mask_node, err=pk["err"], seg_rows=seg, flavour="tgn")
+        z = AttnFn.apply(qf, ngh_dense, ew, spec)
         out = torch.addmm(lw["fcb"], z, lw["G"].t())
         h = F.layer_norm(out + query, (query.shape[1],), lw["lnw"], lw["lnb"], 1e-5)
         x = torch.cat([h, src_feat], dim=1)

@@ -53,7 +53,7 @@ def pair_rows(Rr, H, seg):
 
 
 def train_attn_ref(x, keep, scale):
-    """tests/tgat_ref.attn with the keep mask, and the backward in closed form (the formulas of tgat_train.hip in
+    """tests/tgat_ref.attn with the keep mask, and the backward in closed form (the formulas of csrc/attn_train.h in
     fp64).  x: node [R, N, dn], edge [R, N, de], dt [R, N], tw / tb [dt], qf / gz [R, H, dk], mask [R, N], ew [R, N]
     or None, T, seg; keep uint8 [R H N] or None.  Returns z, d_ew_parts [R, H, N], d_node, d_qf, d_time [2, dt] and
     the magnitude sums d_time's bound is taken from."""

@@ -149,6 +149,41 @@ def test_segments_equal_separate_calls(dev):
     torch.testing.assert_close(two, torch.cat([one_a, one_b]), atol=1e-6, rtol=1e-6)
 
 
+def test_segments_gradient_equals_separate_calls(dev):
+    """d loss / d explain_weights of one stacked call with n_segments=2 against the two batches run separately:
+    the head-major pairing of the d_ew reduction stays inside each segment (the bounds of the gradient test below:
+    the same computation, split differently)."""
+    d = TI.load_batch()
+    m = _model("synth", dev)
+    base = [[x.to(dev) for x in TI.explanation("synth")], [x.to(dev) for x in TI.rand_weights("synth")]]
+    sgs = (d["sg_src"], d["sg_tgt"], d["sg_bgd"])
+    roots = torch.cat([torch.as_tensor(x).long() for x in (d["src"], d["dst"], d["fake"])]).to(dev)
+
+    def cat(i, h, dt):
+        return torch.cat([torch.as_tensor(np.asarray(sg[i][h])).to(dt) for sg in sgs]).to(dev)
+    nodes = [roots, cat(0, 0, torch.int32), cat(0, 1, torch.int32)]
+    eids = [cat(1, 0, torch.int32), cat(1, 1, torch.int32)]
+    times = [cat(2, 0, torch.float64), cat(2, 1, torch.float64)]
+    R = roots.shape[0]
+    gen = torch.Generator().manual_seed(5)
+    w = torch.randn((2 * R, m.n_node_features), generator=gen).to(dev)       # loss = sum(w * embeddings)
+    sep = []
+    for s, ew0 in enumerate(base):
+        ew = [x.clone().requires_grad_(True) for x in ew0]
+        (m.node_embeddings(nodes, eids, times, d["ts_cut"], ew) * w[s * R:(s + 1) * R]).sum().backward()
+        sep.append([x.grad for x in ew])
+    ew2 = [torch.cat([base[0][h], base[1][h]]).requires_grad_(True) for h in (0, 1)]
+    two = m.node_embeddings([x.repeat(2) if x.dim() == 1 else x.repeat(2, 1) for x in nodes],
+                            [x.repeat(2, 1) for x in eids], [x.repeat(2, 1) for x in times], d["ts_cut"], ew2,
+                            n_segments=2)
+    (two * w).sum().backward()
+    for h in (0, 1):
+        ga, gb = ew2[h].grad.double().cpu(), torch.cat([sep[0][h], sep[1][h]]).double().cpu()
+        assert gb.abs().max() > 0
+        assert torch.linalg.norm(ga - gb) <= 1e-4 * torch.linalg.norm(gb)
+        assert (ga - gb).abs().max() <= 1e-6 + 1e-4 * gb.abs().max()
+
+
 @pytest.mark.parametrize("case", CASES)
 def test_explanation_weight_gradient_vs_oracle(dev, case):
     """d BCE(contrast(explain_weights=e), y) / d e through tgn_attn_bwd_kernel + autograd vs torch

@@ -1,4 +1,4 @@
-"""fp64 torch restatement of what the TGAT kernels compute (csrc/tgat_attn.hip), for the C-ABI tests.
+"""fp64 torch restatement of what the attention kernels compute in their TGAT flavour (csrc/attn_kernels.h), for the C-ABI tests.
 
 ``attn`` is one attention pass in the folded form: keys [node | edge | cos(fl(fl(dt w) + b))], scores
 qf_h . key / T, masked scores -1e10, softmax, times the explanation weight, weighted key sum; the mask /

@@ -5,7 +5,7 @@ memory without the dict of lists: per node the last raw message, its timestamp a
 aggregator reads), written with the reference's ordering rules.  Runs in fp32 or fp64 from a ``state_dict``.
 
 Also ``attn_closed_form``: the fp64 closed form of one attention pass's forward and backward (the formulas of
-csrc/tgn_train.hip), with the gradient of a gathered node table, which the kernel tests compare against.
+csrc/attn_train.h and csrc/tgn_train.hip), with the gradient of a gathered node table, which the kernel tests compare against.
 """
 from types import SimpleNamespace
 

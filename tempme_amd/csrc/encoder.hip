@@ -642,8 +642,9 @@ struct WalkLay {
 // in the same order (the results do not change).
 constexpr int PFP = 4;     // weight-fragment ring depth (2, 4, 6 measured: 4 best)
 // waves per SIMD walk_kernel is compiled for, and waves per workgroup (each wave owns its 16 slots and a
-// 12.25 KB LDS stash -- 8.25 KB in the zero-node form --, the workgroup one constant table; 3 waves per SIMD and
-// 8-wave workgroups measured slower)
+// 12.25 KB LDS stash -- 8.25 KB in the zero-node form --, the workgroup one constant table; 3 waves per SIMD
+// measured slower, and so did 8-wave workgroups while a workgroup kept nothing in LDS that two could share).
+// WALK_WPB is the workgroup of every instance but the paired and the pooled persistent zero-node ones (walk_wpb below).
 constexpr int WALK_WAVES = 2;
 constexpr int WALK_WPB = 4;
 
@@ -654,12 +655,30 @@ constexpr int WALK_WPB = 4;
 // pack alone is 72 KB per pass against the fp32 pack's 44 KB and measured slower, with half of it resident the layer
 // streams 36 KB (profiles/gcn_split_ab.txt).
 constexpr int GCN_LDS = 3;
-constexpr int GCN_LDS_FRAGS = GCN_LDS * 12;   // 1 KB each: 4 output tiles x hi / mid / lo per pair step
+// The persistent zero-node instances that large launches take -- paired (PAIR && !SPLIT: the headline's) and pooled
+// (POOL && !SPLIT) -- run 8-wave workgroups, one per CU: the two 4-wave workgroups of a CU each kept their own copy of
+// the resident half, so one workgroup of 8 waves holds the WHOLE pack (72 KB) in the same LDS -- 8 stashes + 72 KB +
+// one constant table = 151,440 B (151,696 B at nqe 13 / 14) of the 163,840 B a workgroup may declare -- and
+// event_gcn's first layer streams nothing (profiles/walk_wg8_ab.txt).  -DTM_WALK_WG8=0 builds them in the 4-wave
+// half-resident form.  Every other instance keeps that form: the single-position scoring and the two-branch
+// instances (the tests' bitwise reference) and the SPLIT ones (small launches, where each workgroup would copy 72 KB
+// before its first pass: measured no faster).
+#ifndef TM_WALK_WG8
+#define TM_WALK_WG8 1
+#endif
+constexpr bool walk_wg8(bool zn, bool pair, bool split, bool pool) { return TM_WALK_WG8 && zn && !split && (pair || pool); }
+constexpr int walk_wpb(bool zn, bool pair, bool split, bool pool) { return walk_wg8(zn, pair, split, pool) ? 8 : WALK_WPB; }
+// event_gcn's resident pair steps of an instance (nsg: the pack's pair steps)
+constexpr int walk_gl(bool zn, bool pair, bool split, bool pool, int nsg) {
+    return walk_wg8(zn, pair, split, pool) ? nsg : GCN_LDS;
+}
 // weight-fragment ring depths of the pair pass (encode_pair): two accumulator sets leave the rings fewer registers,
 // and a lin_event fragment covers twice the MFMA time there
 constexpr int PAIR_LIN_RING = 6, PAIR_GCN_RING = 6;
-// the k-th pair step executed: streamed steps (gl .. ns - 1) and resident ones (0 .. gl - 1) alternate,
-// a streamed one first, so a streamed step's refills have two steps to arrive
+// the k-th pair step executed.  The order is that of the half-resident form (gl = GCN_LDS) in every instance,
+// whatever is resident, so a column's sum does not depend on the instance: there the streamed steps (gl .. ns - 1)
+// and the resident ones (0 .. gl - 1) alternate, a streamed one first, so a streamed step's refills have two steps
+// to arrive (3, 0, 4, 1, 5, 2)
 constexpr int gcn_step(int k, int gl, int ns) {
     const int nstr = ns - gl, m = nstr < gl ? nstr : gl;
     if (k < 2 * m) return (k & 1) ? k / 2 : gl + k / 2;
@@ -1036,12 +1055,16 @@ __device__ __forceinline__ void load_et(const WalkArgs &a, int32_t e, float4 (&e
 // activations are split between this step's MFMAs.  The ring's last refills request the next phase's first PFP
 // fragments (nx, returned in pre) or, AGAIN (the pair pass: the other column set's layer follows), the pack's first
 // streamed pair step once more, left in gb.  D: the ring's depth (the ring holds fragments 0 .. D - 1 on entry).
-template <int NTD, bool AGAIN, int D, class Extra>
+// GL: the instance's resident pair steps (walk_gl).  GL == NSG, the whole pack resident: every pair comes from LDS,
+// gb is not touched and pre, which then holds nx's fragments on entry (requested by lin_event's ring), passes through.
+template <int NTD, bool AGAIN, int GL, int D, class Extra>
 __device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const float4 *gl, const floatx4 (&L)[NTD],
                                        float4 (&gb)[D], Extra &&extra, floatx4 (&Hs)[4], float4 (&pre)[PFP],
                                        const NextFr &nx) {
-    constexpr int NSG = (NTD + 1) / 2, GL = GCN_LDS, N = (NSG - GL) * 12;
-    static_assert(N % D == 0 && D >= PFP, "event_gcn ring depth");
+    constexpr int NSG = (NTD + 1) / 2, N = (NSG - GL) * 12;
+    constexpr bool RES = GL == NSG;                      // the whole pack resident: no ring, pre passes through
+    static_assert(GL >= 1 && GL <= NSG, "event_gcn's resident steps");
+    static_assert(RES || (N % D == 0 && D >= PFP), "event_gcn ring depth");
     const int vo = lane_id() * 16, ln = lane_id();
     auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
     int zg = 0;
@@ -1058,10 +1081,10 @@ __device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const
     };
     // the six fragments (tile t: hi, mid, lo; tile t + 1: hi, mid, lo) of pair p = (executed step p / 2, t = 2 (p & 1))
     auto fetch = [&](int p, float4 (&w)[6]) {
-        const int u = gcn_step(p / 2, GL, NSG), t = 2 * (p & 1);
+        const int u = gcn_step(p / 2, GCN_LDS, NSG), t = 2 * (p & 1);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-            if (u < GL) w[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
+            if (RES || u < GL) w[k] = gl[((u * 4 + t) * 3 + k) * 64 + ln];
             else w[k] = take(((u - GL) * 4 + t) * 3 + k);
         }
     };
@@ -1077,7 +1100,7 @@ __device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const
     };
     Split3 xb;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) act(xb, gcn_step(0, GL, NSG), j);
+    for (int j = 0; j < 8; ++j) act(xb, gcn_step(0, GCN_LDS, NSG), j);
     float4 wb[2][6];
     fetch(0, wb[0]);
 #pragma unroll
@@ -1107,13 +1130,13 @@ __device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const
             Hs[t + 1] = TM_MF32(h1, xb.h, Hs[t + 1]);
             if (k + 1 < NSG) {
 #pragma unroll
-                for (int j = 2 * t; j < 2 * t + 4; ++j) act(xn, gcn_step(k + 1, GL, NSG), j);
+                for (int j = 2 * t; j < 2 * t + 4; ++j) act(xn, gcn_step(k + 1, GCN_LDS, NSG), j);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
         xb = xn;
     }
-    if constexpr (!AGAIN) {
+    if constexpr (!AGAIN && !RES) {
 #pragma unroll
         for (int k = 0; k < PFP; ++k) pre[k] = gb[(N + k) % D];
     }
@@ -1131,7 +1154,7 @@ __device__ __forceinline__ void gcn_zn(__amdgpu_buffer_rsrc_t wr, int vog, const
 // zero for those inputs, so they contribute nothing.
 // SEF (streamed edge features, EQ_MAX*16 < de <= 176): ef holds the 32-wide K steps 0 and 1 (loaded during the
 // previous pass); step s + 2's two float4 are loaded while step s's MFMAs run.
-template <int NQE, int NTD, bool SEF, int Q0, bool ZN, class Extra>
+template <int NQE, int NTD, bool SEF, int Q0, bool ZN, int GL, class Extra>
 __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs,
                                                 const PosIn &pi, const float (&ef)[EQ_MAX][4],
                                                 float4 (&et)[ETAB_N(Q0)], Extra &&extra, int p, floatx4 (&H)[8],
@@ -1169,11 +1192,15 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
     // (tiles 0..3 x hi / mid / lo) in gb; `pre` carries nothing into event_gcn then (in the two-branch instances it
     // carries G1's K step 0, tiles 0..3).  The pack's offset off wr rides in the lane offset and the fragment
     // offsets on an opaque zero, as for ev3 below.
-    constexpr int NSG = (NTD + 1) / 2, GD = 12, GL = GCN_LDS;
-    static_assert(GL >= 1 && GL < NSG, "event_gcn's resident steps");
+    // RES (GL == NSG, the 8-wave instances): the whole pack is resident, there is no streamed step and no gb; lin_event's
+    // ring then hands over the first PFP fragments of the phase after event_gcn (nx) in `pre`, as in the two-branch
+    // instances it hands over G1's, and event_gcn passes them through.
+    constexpr int NSG = (NTD + 1) / 2, GD = 12;
+    constexpr bool RES = ZN && GL == NSG;
+    static_assert(!ZN || (GL >= 1 && GL <= NSG), "event_gcn's resident steps");
     const int vog = lane_id() * 16 + 16 * (int)(P.g13 - P.kv.w);
     auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
-    float4 gb[ZN ? GD : 1];
+    float4 gb[ZN && !RES ? GD : 1];
     (void)vog, (void)goff, (void)gb;
     constexpr int JN = 3;                                // node tiles in flight in event_gcn's K loop
     float4 rs[JN], rt[JN];
@@ -1265,7 +1292,9 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
                 auto take = [&](int i) {
                     const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
                     if (i + D < N) buf[i % D] = wload3(i + D);
-                    else if constexpr (ZN) buf[i % D] = wloadg(i + D - N);
+                    else if constexpr (RES) {
+                        if (i + D - N < PFP) buf[i % D] = wload(wr, vo, nx.o[i + D - N]);
+                    } else if constexpr (ZN) buf[i % D] = wloadg(i + D - N);
                     else if (i + D - N < PFP) buf[i % D] = wload(wr, vo, g1f(i + D - N));
                     return v;
                 };
@@ -1313,7 +1342,14 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         }
         // G1's first fragments: in the ring's slots after a full K loop; the slot pass (K loop cut at qt)
         // requests them now
-        if constexpr (ZN) {
+        if constexpr (RES) {
+            if (p == 2) {
+#pragma unroll
+                for (int k = 0; k < PFP; ++k) buf[(N + k) % D] = wload(wr, vo, nx.o[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < PFP; ++k) pre[k] = buf[(N + k) % D];
+        } else if constexpr (ZN) {
             if (p == 2) {
 #pragma unroll
                 for (int k = 0; k < D; ++k) buf[(N + k) % D] = wloadg(k);
@@ -1345,7 +1381,8 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
     }
     if constexpr (ZN) {
         // one branch (gcn_zn); its ring's last refills request the next phase's first PFP fragments (nx)
-        gcn_zn<NTD, false, GD>(wr, vog, gl, L, gb, extra, Hs, pre, nx);
+        // (RES: nx's fragments are in pre already, requested by lin_event's ring)
+        gcn_zn<NTD, false, GL, RES ? 1 : GD>(wr, vog, gl, L, gb, extra, Hs, pre, nx);
     } else {
         const int vo = lane_id() * 16;
         float4 wq[2][4];
@@ -1414,7 +1451,7 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
 // together do not fit the register file), set 1's L kept live meanwhile and the g13 pack's streamed steps requested
 // once per set; `extra` is placed in set 1's layer.  On return pre holds nx's fragments.
 // Stamps: 1 table rows, 2 lin_event (both sets), 3 event_gcn set 0, 4 event_gcn set 1, 5 relu.
-template <int NQE, int NTD, int Q0, class Extra>
+template <int NQE, int NTD, int Q0, int GL, class Extra>
 __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_rsrc_t wr, const float *cs,
                                             const PosIn &pi0, const PosIn &pi1, const float4 (&et0)[NTD],
                                             const float4 (&et1)[NTD], Extra &&extra, floatx4 (&U0)[4],
@@ -1436,16 +1473,21 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
         L1[t] = floatx4{et1[t].x, et1[t].y, et1[t].z, et1[t].w};
     }
     TM_STAMP(1);
-    constexpr int NSG = (NTD + 1) / 2, GL = GCN_LDS;
+    // RES (the whole g13 pack resident, the 8-wave instances): no streamed pair step and no gb; lin_event's last
+    // refills request nx's fragments instead, which both sets' event_gcn layers pass through in pre
+    constexpr int NSG = (NTD + 1) / 2;
+    constexpr bool RES = GL == NSG;
     const int vog = lane_id() * 16 + 16 * (int)(P.g13 - P.kv.w);
-    constexpr int GD = PAIR_GCN_RING;
+    constexpr int GD = RES ? 1 : PAIR_GCN_RING;
     float4 gb[GD];
+    (void)vog, (void)gb;
     {
         // ring and fragment order as in encode_position (K-outer; fragment i = (step, tile, part)); the ring's last
         // refills take the g13 pack's first streamed fragments for event_gcn
         constexpr int NS = C::NS, S0 = Q0 / 2;
         constexpr int N = NTD * (NS - S0) * 3, D = PAIR_LIN_RING;
-        static_assert(D >= PFP && D <= N && D % 3 == 0 && D <= GD, "lin_event ring depth");
+        static_assert(D >= PFP && D <= N && D % 3 == 0 && (RES || D <= GD), "lin_event ring depth");
+        const int vo = lane_id() * 16;
         const int vo3 = lane_id() * 16 + 16 * (int)(P.ev3 - P.kv.w);
         auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
         auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
@@ -1457,6 +1499,7 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
         auto wloadg = [&](int i) {
             return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, z3 + goff(i) * 16, 0));
         };
+        (void)wloadg, (void)vo;
         float4 buf[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload3(i);
@@ -1493,7 +1536,9 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
             auto take = [&](int i) {
                 const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
                 if (i + D < N) buf[i % D] = wload3(i + D);
-                else buf[i % D] = wloadg(i + D - N);
+                else if constexpr (RES) {
+                    if (i + D - N < PFP) buf[i % D] = wload(wr, vo, nx.o[i + D - N]);
+                } else buf[i % D] = wloadg(i + D - N);
                 return v;
             };
 #pragma unroll
@@ -1518,20 +1563,25 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
             xs0 = xn0;
             xs1 = xn1;
         }
+        if constexpr (RES) {
 #pragma unroll
-        for (int k = 0; k < GD; ++k) gb[k] = k < D ? buf[(N + k) % D] : wloadg(k);
+            for (int k = 0; k < PFP; ++k) pre[k] = buf[(N + k) % D];
+        } else {
+#pragma unroll
+            for (int k = 0; k < GD; ++k) gb[k] = k < D ? buf[(N + k) % D] : wloadg(k);
+        }
     }
     TM_STAMP(2);
     floatx4 Hs[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) Hs[t] = ldsx4(cs + C::G1, t);
-    gcn_zn<NTD, true, GD>(wr, vog, gl, L0, gb, [](int) {}, Hs, pre, nx);
+    gcn_zn<NTD, true, GL, GD>(wr, vog, gl, L0, gb, [](int) {}, Hs, pre, nx);
 #pragma unroll
     for (int t = 0; t < 4; ++t) U0[t] = relu4(Hs[t]);
     TM_STAMP(3);
 #pragma unroll
     for (int t = 0; t < 4; ++t) Hs[t] = ldsx4(cs + C::G1, t);
-    gcn_zn<NTD, false, GD>(wr, vog, gl, L1, gb, extra, Hs, pre, nx);
+    gcn_zn<NTD, false, GL, GD>(wr, vog, gl, L1, gb, extra, Hs, pre, nx);
     TM_STAMP(4);
 #pragma unroll
     for (int t = 0; t < 4; ++t) U1[t] = relu4(Hs[t]);
@@ -1701,9 +1751,11 @@ __device__ __forceinline__ float score_dot(const Stash<ZN ? 4 : 8> &st, const fl
 // slot pass and one pass per walk -- 1 + M passes, SPLIT 2 -- and lin_event's weights are streamed once per walk.
 template <int NQE, int NTD, bool SEF = false, int QE0 = 0, bool SPLIT = false, bool ZN = false, bool POOL = false,
           bool PAIR = false>
-__global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk_kernel(WalkArgs a) {
+__global__ void __launch_bounds__(64 * walk_wpb(ZN, PAIR, SPLIT, POOL), WALK_WAVES) walk_kernel(WalkArgs a) {
     static_assert(!PAIR || (ZN && QE0 > 0 && !SEF && !POOL), "the pair pass: zero-node table mode, not pooled");
     using C = WalkConsts<NQE, NTD>;
+    constexpr int WPB = walk_wpb(ZN, PAIR, SPLIT, POOL);          // waves per workgroup
+    constexpr int GL = walk_gl(ZN, PAIR, SPLIT, POOL, (NTD + 1) / 2);   // event_gcn's resident pair steps
     constexpr int NA = ZN ? 4 : 8;                      // tiles of a position's hidden vector (ZN: U alone)
     const EncW &P = a.P;
     const int lane = threadIdx.x & 63, col = lane & 15;
@@ -1740,7 +1792,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     int32_t j;
     coords(unit, valid, eg, j);
     // LDS: per-wave stash of the slot's position-2 results (12.25 KB per wave; ZN 8.25 KB), then the constant table
-    __shared__ Stash<NA> stash[WALK_WPB];
+    __shared__ Stash<NA> stash[WPB];
     __shared__ float4 cs4[(C::SIZE + 3) / 4];
     float *cs = reinterpret_cast<float *>(cs4);
 #ifdef TM_TRACE
@@ -1748,12 +1800,12 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
     int trn = 0;
     const unsigned long long tr0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    // ZN: event_gcn's resident weight fragments (the g13 pack's pair steps 0 .. GCN_LDS - 1, in (step, tile, part)
-    // order; see encode_position)
-    __shared__ float4 gl[ZN ? GCN_LDS_FRAGS * 64 : 1];
+    // ZN: event_gcn's resident weight fragments (the g13 pack's pair steps 0 .. GL - 1, in (step, tile, part)
+    // order; see encode_position), 1 KB each: 4 output tiles x hi / mid / lo per pair step
+    __shared__ float4 gl[ZN ? GL * 12 * 64 : 1];
     if constexpr (ZN) {
         constexpr int NSG = (NTD + 1) / 2;
-        for (int i = threadIdx.x; i < GCN_LDS_FRAGS * 64; i += blockDim.x) {
+        for (int i = threadIdx.x; i < GL * 12 * 64; i += blockDim.x) {
             const int f = i >> 6, l = i & 63;
             gl[i] = P.g13[((((f / 3) % 4) * NSG + f / 12) * 3 + f % 3) * 64 + l];
         }
@@ -1872,7 +1924,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
             // the next pass's lin_event fragments
             if constexpr (PAIR) {
                 floatx4 U0[4], U1[4];
-                encode_pair<NQE, NTD, QE0>(a, wr, cs, cur, cur1, et, et1, extra, U0, U1, pre,
+                encode_pair<NQE, NTD, QE0, GL>(a, wr, cs, cur, cur1, et, et1, extra, U0, U1, pre,
                                            pair_first<4>(FoldLay::A1GZ / 4), T, gl);
                 load_et<QE0>(a, nxt.edge(), et);
                 load_et<QE0>(a, nxt1.edge(), et1);
@@ -1891,7 +1943,7 @@ __global__ void __launch_bounds__(64 * WALK_WPB, 4 * WALK_WAVES / WALK_WPB) walk
         // lin_event fragments
         const NextFr nx_pos = ZN ? pair_first<4>(p == 2 ? FoldLay::A1DZ / 4 : FoldLay::A1GZ / 4)
                                  : pair_first<8>(p == 2 ? FoldLay::A1D / 4 : FoldLay::A1G / 4);
-        encode_position<NQE, NTD, SEF, QE0, ZN>(a, wr, cs, cur, ef, et, extra, p, H, pre,
+        encode_position<NQE, NTD, SEF, QE0, ZN, GL>(a, wr, cs, cur, ef, et, extra, p, H, pre,
                                                 p == 0 ? lin0 : nx_pos, T, gl);
         if constexpr (QE0 == 0) load_ef(a, nxt.edge(), ef);
         else load_et<QE0>(a, nxt.edge(), et);
@@ -2646,20 +2698,24 @@ static bool walk_split(int64_t units, int32_t M) { return units * M <= 3 * WALK_
 
 // a.ticket zeroed on the stream before the launch unless walk_split (encoder_fwd_impl)
 template <int NQE, bool SEF, int Q0, bool ZN, bool POOL, bool PAIR>
-static void launch_walk_as(const WalkArgs &a, unsigned blocks, hipStream_t s) {
+static void launch_walk_as(const WalkArgs &a, hipStream_t s) {
     const int64_t units = (a.n_slots + 15) / 16;
     if (walk_split(units, a.M)) {
-        const unsigned sb = (unsigned)((units * a.M + WALK_WPB - 1) / WALK_WPB);
-        walk_kernel<NQE, 11, SEF, Q0, true, ZN, POOL, PAIR><<<dim3(sb), 64 * WALK_WPB, 0, s>>>(a);
+        constexpr int WPB = walk_wpb(ZN, PAIR, true, POOL);
+        const unsigned sb = (unsigned)((units * a.M + WPB - 1) / WPB);
+        walk_kernel<NQE, 11, SEF, Q0, true, ZN, POOL, PAIR><<<dim3(sb), 64 * WPB, 0, s>>>(a);
         return;
     }
+    // the instance's waves per workgroup: one wave per unit, then
+    constexpr int WPB = walk_wpb(ZN, PAIR, false, POOL);
+    unsigned blocks = (unsigned)((units + WPB - 1) / WPB);
     // one round of resident workgroups (occupancy x CUs of the current device), cached per instance
     static int cap[64] = {};
     int dev = 0;
     if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64) {
         if (cap[dev] == 0) {
             int per_cu = 0, cus = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR>, 64 * WALK_WPB, 0) ==
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR>, 64 * WPB, 0) ==
                     hipSuccess &&
                 hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0 &&
                 cus > 0)
@@ -2671,17 +2727,17 @@ static void launch_walk_as(const WalkArgs &a, unsigned blocks, hipStream_t s) {
     }
     const int dbg = debug_opt(TM_DEBUG_WALK_BLOCKS);   // A/B of smaller persistent grids (tools/walk_grid_ab.sh)
     if (dbg > 0 && blocks > (unsigned)dbg) blocks = (unsigned)dbg;
-    walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR><<<dim3(blocks), 64 * WALK_WPB, 0, s>>>(a);
+    walk_kernel<NQE, 11, SEF, Q0, false, ZN, POOL, PAIR><<<dim3(blocks), 64 * WPB, 0, s>>>(a);
 }
 
 // the zero-node table-mode instances run the pair pass unless tm_debug_set(TM_DEBUG_WALK_SINGLE, 1) asks for the
 // single-position pass (tests compare the two bit for bit)
 template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false, bool POOL = false>
-static void launch_walk(const WalkArgs &a, unsigned blocks, hipStream_t s) {
+static void launch_walk(const WalkArgs &a, hipStream_t s) {
     if constexpr (ZN && Q0 > 0 && !SEF && !POOL) {
-        if (!debug_opt(TM_DEBUG_WALK_SINGLE)) return launch_walk_as<NQE, SEF, Q0, ZN, POOL, true>(a, blocks, s);
+        if (!debug_opt(TM_DEBUG_WALK_SINGLE)) return launch_walk_as<NQE, SEF, Q0, ZN, POOL, true>(a, s);
     }
-    launch_walk_as<NQE, SEF, Q0, ZN, POOL, false>(a, blocks, s);
+    launch_walk_as<NQE, SEF, Q0, ZN, POOL, false>(a, s);
 }
 
 extern "C" int tm_encoder_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
@@ -2742,30 +2798,29 @@ static int encoder_fwd_impl(const tm_weights *w, const float *n_feat, const floa
         // the unit counter of a dynamic persistent launch lives in the workspace's F region (unused by this path)
         WalkArgs a{P, n_slots, W, M, B * W, n_feat, e_feat, node6, eid3, cat, ts3, cnt, stdv, cut, out_imp, etab,
                    reinterpret_cast<uint32_t *>(F)};
-        const unsigned blocks = (unsigned)((units + WALK_WPB - 1) / WALK_WPB);
         const int q0 = etab ? etab_q0(P) : 0;
         if (!walk_split(units, M)) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
         pe = prof_begin(s);
         if (q0 == 2 && w->node_zero) {   // edge table, zero node features: one event_gcn branch (ZN)
-            if (nqe == 11) launch_walk<11, false, 2, true>(a, blocks, s);
-            else if (nqe == 12) launch_walk<12, false, 2, true>(a, blocks, s);
-            else if (nqe == 13) launch_walk<13, false, 2, true>(a, blocks, s);
-            else launch_walk<14, false, 2, true>(a, blocks, s);
+            if (nqe == 11) launch_walk<11, false, 2, true>(a, s);
+            else if (nqe == 12) launch_walk<12, false, 2, true>(a, s);
+            else if (nqe == 13) launch_walk<13, false, 2, true>(a, s);
+            else launch_walk<14, false, 2, true>(a, s);
         } else if (q0 == 2) {        // edge table: lin_event from K step 2
-            if (nqe == 11) launch_walk<11, false, 2>(a, blocks, s);
-            else if (nqe == 12) launch_walk<12, false, 2>(a, blocks, s);
-            else if (nqe == 13) launch_walk<13, false, 2>(a, blocks, s);
-            else launch_walk<14, false, 2>(a, blocks, s);
+            if (nqe == 11) launch_walk<11, false, 2>(a, s);
+            else if (nqe == 12) launch_walk<12, false, 2>(a, s);
+            else if (nqe == 13) launch_walk<13, false, 2>(a, s);
+            else launch_walk<14, false, 2>(a, s);
         } else if (q0 == 10) {   // edge table: lin_event from K step 10 (no streamed edge features)
-            if (nqe == 21) launch_walk<21, false, 10>(a, blocks, s);
-            else launch_walk<22, false, 10>(a, blocks, s);
+            if (nqe == 21) launch_walk<21, false, 10>(a, s);
+            else launch_walk<22, false, 10>(a, s);
         } else if (wide) {
-            if (nqe == 21) launch_walk<21, true>(a, blocks, s);
-            else launch_walk<22, true>(a, blocks, s);
-        } else if (nqe == 11) launch_walk<11>(a, blocks, s);
-        else if (nqe == 12) launch_walk<12>(a, blocks, s);
-        else if (nqe == 13) launch_walk<13>(a, blocks, s);
-        else launch_walk<14>(a, blocks, s);
+            if (nqe == 21) launch_walk<21, true>(a, s);
+            else launch_walk<22, true>(a, s);
+        } else if (nqe == 11) launch_walk<11>(a, s);
+        else if (nqe == 12) launch_walk<12>(a, s);
+        else if (nqe == 13) launch_walk<13>(a, s);
+        else launch_walk<14>(a, s);
         TM_CHECK_LAUNCH();
         prof_end("walk_kernel", s, pe);
         return TM_OK;
@@ -2794,28 +2849,27 @@ extern "C" int64_t tm_encoder_pool_workspace_bytes(const tm_weights *w, int64_t 
 }
 
 // the fused kernel's POOL instance for these dims (the instance table of encoder_fwd_impl)
-static void launch_walk_pool(const WalkArgs &a, int nqe, bool wide, int q0, int node_zero, unsigned blocks,
-                             hipStream_t s) {
+static void launch_walk_pool(const WalkArgs &a, int nqe, bool wide, int q0, int node_zero, hipStream_t s) {
     if (q0 == 2 && node_zero) {
-        if (nqe == 11) launch_walk<11, false, 2, true, true>(a, blocks, s);
-        else if (nqe == 12) launch_walk<12, false, 2, true, true>(a, blocks, s);
-        else if (nqe == 13) launch_walk<13, false, 2, true, true>(a, blocks, s);
-        else launch_walk<14, false, 2, true, true>(a, blocks, s);
+        if (nqe == 11) launch_walk<11, false, 2, true, true>(a, s);
+        else if (nqe == 12) launch_walk<12, false, 2, true, true>(a, s);
+        else if (nqe == 13) launch_walk<13, false, 2, true, true>(a, s);
+        else launch_walk<14, false, 2, true, true>(a, s);
     } else if (q0 == 2) {
-        if (nqe == 11) launch_walk<11, false, 2, false, true>(a, blocks, s);
-        else if (nqe == 12) launch_walk<12, false, 2, false, true>(a, blocks, s);
-        else if (nqe == 13) launch_walk<13, false, 2, false, true>(a, blocks, s);
-        else launch_walk<14, false, 2, false, true>(a, blocks, s);
+        if (nqe == 11) launch_walk<11, false, 2, false, true>(a, s);
+        else if (nqe == 12) launch_walk<12, false, 2, false, true>(a, s);
+        else if (nqe == 13) launch_walk<13, false, 2, false, true>(a, s);
+        else launch_walk<14, false, 2, false, true>(a, s);
     } else if (q0 == 10) {
-        if (nqe == 21) launch_walk<21, false, 10, false, true>(a, blocks, s);
-        else launch_walk<22, false, 10, false, true>(a, blocks, s);
+        if (nqe == 21) launch_walk<21, false, 10, false, true>(a, s);
+        else launch_walk<22, false, 10, false, true>(a, s);
     } else if (wide) {
-        if (nqe == 21) launch_walk<21, true, 0, false, true>(a, blocks, s);
-        else launch_walk<22, true, 0, false, true>(a, blocks, s);
-    } else if (nqe == 11) launch_walk<11, false, 0, false, true>(a, blocks, s);
-    else if (nqe == 12) launch_walk<12, false, 0, false, true>(a, blocks, s);
-    else if (nqe == 13) launch_walk<13, false, 0, false, true>(a, blocks, s);
-    else launch_walk<14, false, 0, false, true>(a, blocks, s);
+        if (nqe == 21) launch_walk<21, true, 0, false, true>(a, s);
+        else launch_walk<22, true, 0, false, true>(a, s);
+    } else if (nqe == 11) launch_walk<11, false, 0, false, true>(a, s);
+    else if (nqe == 12) launch_walk<12, false, 0, false, true>(a, s);
+    else if (nqe == 13) launch_walk<13, false, 0, false, true>(a, s);
+    else launch_walk<14, false, 0, false, true>(a, s);
 }
 
 extern "C" int tm_encoder_pool_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
@@ -2853,12 +2907,11 @@ extern "C" int tm_encoder_pool_fwd(const tm_weights *w, const float *n_feat, con
             const int64_t units = (n_slots + 15) / 16;
             WalkArgs a{P, n_slots, W, M, B * W, n_feat, e_feat, node6, eid3, cat, ts3, cnt, stdv, cut, part, etab,
                        reinterpret_cast<uint32_t *>(F), wgt};
-            const unsigned blocks = (unsigned)((units + WALK_WPB - 1) / WALK_WPB);
             const bool split = walk_split(units, M);
             if (!split) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
             n_part = split ? W : W / M;
             pe = prof_begin(s);
-            launch_walk_pool(a, nqe, wide, etab ? etab_q0(P) : 0, w->node_zero, blocks, s);
+            launch_walk_pool(a, nqe, wide, etab ? etab_q0(P) : 0, w->node_zero, s);
             TM_CHECK_LAUNCH();
             prof_end("walk_pool_kernel", s, pe);
         } else {

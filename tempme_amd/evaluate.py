@@ -32,7 +32,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .train import batch_from_pack, encode_sides, explain_sides, prepare_step
+from .train import (base_is_tgat, batch_from_pack, encode_sides, explain_sides, explained_contrast, prepare_step,
+                    split_stacked_weights)
 
 BATCH_FIGURES = ("aps", "auc", "acc", "fid_prob", "fid_logit", "loss", "pred_loss", "kl_loss")
 RATIO_FIGURES = ("ratio_aps", "ratio_auc", "ratio_acc", "ratio_prob", "ratio_logit")
@@ -79,14 +80,19 @@ def eval_batch(args, base_model, explainer, batch, device_metrics=False):
     criterion = torch.nn.BCEWithLogitsLoss()
     row = np.full(len(FIGURES) + 1, np.nan)
     row[THRESHOLD_RAN] = 0.0
+    tgat = base_is_tgat(explainer, base_model)
+
+    def full_explanation():
+        # retrieve_explanation(training=False) for threshold_test; its tgat branch takes the per-side 6-list
+        expl0 = explain_sides(explainer, batch, imps, False)
+        return split_stacked_weights(*expl0, flat=True) if tgat else expl0
     with torch.no_grad():
         kw, pos_out_ori, neg_out_ori, y_ori = prepare_step(base_model, batch)
         explainer.eval()
         imps = encode_sides(explainer, batch)
         explanation = explain_sides(explainer, batch, imps, bool(args.if_bern))
         sg_s, sg_t, sg_b = batch.subgraphs
-        pos_logit, neg_logit = base_model.contrast(batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, sg_s,
-                                                   sg_t, sg_b, explain_weights=explanation, **kw)
+        pos_logit, neg_logit = explained_contrast(base_model, batch, explanation, kw, tgat)
         pred = torch.cat([pos_logit, neg_logit], dim=0)
         pred_loss = criterion(pred, y_ori)
         B, W = imps[0].shape[0], imps[0].shape[1]
@@ -107,10 +113,9 @@ def eval_batch(args, base_model, explainer, batch, device_metrics=False):
             dev = y_pred.device
             head = torch.stack([x.reshape(()) for x in (acc, fid_prob, fid_logit, loss, pred_loss, kl_loss)]).double()
             if getattr(args, "test_threshold", False):
-                expl0 = explain_sides(explainer, batch, imps, False)
-                ratio = fidelity.threshold_test(args, expl0, base_model, batch.src, batch.dst, batch.fake, batch.ts,
-                                                batch.e_idx, pos_out_ori, neg_out_ori, y_ori, sg_s, sg_t, sg_b,
-                                                device_metrics=True)
+                ratio = fidelity.threshold_test(args, full_explanation(), base_model, batch.src, batch.dst, batch.fake,
+                                                batch.ts, batch.e_idx, pos_out_ori, neg_out_ori, y_ori, sg_s, sg_t,
+                                                sg_b, device_metrics=True)
                 ran = torch.ones(1, dtype=torch.float64, device=dev)
             else:
                 ratio = torch.full((len(RATIO_FIGURES),), float("nan"), dtype=torch.float64, device=dev)
@@ -121,10 +126,9 @@ def eval_batch(args, base_model, explainer, batch, device_metrics=False):
         row[:8] = (aps, auc, float(acc), float(fid_prob), float(fid_logit), float(loss), float(pred_loss),
                    float(kl_loss))
         if getattr(args, "test_threshold", False):
-            expl0 = explain_sides(explainer, batch, imps, False)
-            row[8:THRESHOLD_RAN] = fidelity.threshold_test(args, expl0, base_model, batch.src, batch.dst, batch.fake,
-                                                           batch.ts, batch.e_idx, pos_out_ori, neg_out_ori, y_ori,
-                                                           sg_s, sg_t, sg_b)
+            row[8:THRESHOLD_RAN] = fidelity.threshold_test(args, full_explanation(), base_model, batch.src, batch.dst,
+                                                           batch.fake, batch.ts, batch.e_idx, pos_out_ori, neg_out_ori,
+                                                           y_ori, sg_s, sg_t, sg_b)
             row[THRESHOLD_RAN] = 1.0
     return row
 

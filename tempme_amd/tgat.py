@@ -25,6 +25,11 @@ LayerNorm, the two-branch MergeLayer) runs as torch ops on the device (different
 three passes: ``tm_tgat_attn_bwd`` returns d ew, the gradient of the dense neighbour table (h1') and the
 gradient of the folded query (through h0').  On these paths the base model is frozen: its parameters get no .grad.
 
+For the explainer's drivers (train.py, evaluate.py) ``prepare_contrast`` builds the inputs a contrast derives from
+its batch once (``contrast(..., prepared=...)`` shares them between the original and the explained contrast of a step)
+and ``contrast(..., stacked_weights=(hop-1 [3B, N], hop-2 [3B, N^2]))`` takes the three sides' weights as the two
+tensors ``explain_groups`` returns: ``exp_weights=[[s, t], [s, b]]`` of their views without a split and a cat.
+
 Training the base itself (learn_base.py) is opt-in: after ``model.train_on_hip()``, ``model.train()`` calls of
 ``contrast(..., if_explain=False)`` / ``get_node_emb`` with gradients enabled run ``tm_tgat_attn_train_fwd`` /
 ``tm_tgat_attn_train_bwd`` (csrc/attn_train.h, ``attn_op.TrainAttnFn``): the attention dropout as a keep mask
@@ -40,6 +45,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from .attn_op import AttnFn, TrainAttnFn, _as_dev
+from .tgn import _cat_rows
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -254,12 +260,17 @@ class TGAT(nn.Module):
         return pack
 
     # -------------------------------------------------------------- forward pieces
-    def _attn_pass(self, pk, mi, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, ew, seg):
-        """One AttnModel.forward (TGAT.py:362-386) over R source rows -> [R, feat]."""
+    def _query(self, lw, src, src_t, R):
+        """The query rows [src | 0 (d_edge) | src_t] of a pass and their folded projection."""
+        query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)      # [R, dk]
+        return query, (query @ lw["Pt"]).contiguous()                                    # [R, H*dk]
+
+    def _attn_pass(self, pk, mi, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, ew, seg, q=None):
+        """One AttnModel.forward (TGAT.py:362-386) over R source rows -> [R, feat]; ``q``: ``_query``'s pair
+        for these rows when it is already built."""
         lw = pk["models"][mi]
         H, dk, fd = lw["H"], lw["dk"], self.feat_dim
-        query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)      # [R, dk]
-        qf = (query @ lw["Pt"]).contiguous()                                             # [R, H*dk]
+        query, qf = q if q is not None else self._query(lw, src, src_t, R)
         spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=fd, d_edge=self.e_feat_dim, d_time=self.time_dim,
                     node_rows=pk["tab"].shape[0], edge_rows=pk["etab"].shape[0], head_major=self.head_major_rows,
                     temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"],
@@ -284,10 +295,12 @@ class TGAT(nn.Module):
         of a contrast, times the ratios of a threshold_test): every row gives the same result as in its own
         call, the head-major pairing stays inside its segment.  cut_time: one time per row, or per row of
         one segment (repeated)."""
-        train = explain_weights is None and self._train_hip_ok()
-        self._check_mode(explain_weights)
-        pk = None if train else self._pack()
-        dev = self._dev() if train else pk["dev"]
+        return self._embed(self._prep_inputs(nodes, eids, times, cut_time, n_segments), explain_weights)
+
+    def _prep_inputs(self, nodes, eids, times, cut_time, n_segments=1):
+        """What node_embeddings derives from its inputs before any weight is read: the node, edge-id and time
+        tensors on the device in the kernels' dtypes and the two time offsets (a dict)."""
+        dev = self._dev()
         i32, f64 = torch.int32, torch.float64
         n0 = _as_dev(nodes[0], dev, torch.long).reshape(-1)
         R = n0.shape[0]
@@ -308,17 +321,39 @@ class TGAT(nn.Module):
         t2 = _as_dev(times[1], dev, f64).reshape(R, N, N)
         dt1 = (cut.view(R, 1) - t1).float().contiguous()                   # retrieve_time_features :653-666
         dt2 = (t1.view(R, N, 1) - t2).float().contiguous()
+        return dict(dev=dev, R=R, N=N, seg=seg, n_segments=n_segments, n0=n0, n1=n1, n2=n2, e1=e1, e2=e2, dt1=dt1,
+                    dt2=dt2)
+
+    def _embed(self, x, explain_weights=None):
+        """The three passes of node_embeddings on ``_prep_inputs``' dict ``x``."""
+        train = explain_weights is None and self._train_hip_ok()
+        self._check_mode(explain_weights)
+        R, N, seg = x["R"], x["N"], x["seg"]
+        n0, n1, n2, e1, e2, dt1, dt2 = (x[k] for k in ("n0", "n1", "n2", "e1", "e2", "dt1", "dt2"))
         if train:
-            return self._embed_train(dev, R, N, seg, n0, n1, n2, e1, e2, dt1, dt2)
+            return self._embed_train(x["dev"], R, N, seg, n0, n1, n2, e1, e2, dt1, dt2)
+        pk = self._pack()
+        dev = pk["dev"]
         ew1 = ew2 = None
         if explain_weights is not None:
             ew1 = explain_weights[0].to(dev, torch.float32).reshape(R, N).contiguous()
             ew2 = explain_weights[1].to(dev, torch.float32).reshape(R * N, N).contiguous()
         tab, freq, phase = pk["tab"], pk["freq"], pk["phase"]
         t_root = pk["t0"].expand(R, -1)
-        t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)             # two roundings (mul, then add)
-        h0 = self._attn_pass(pk, 0, tab[n0], t_root, R, N, n1, None, e1, dt1, n1, ew1, seg)
-        h1 = self._attn_pass(pk, 0, tab[n1.reshape(-1).long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N)
+        # the queries of passes 1 and 2 depend on the batch and the frozen pack only: prepare_contrast's dict
+        # keeps them, so the contrasts that share it (without and with weights) fold them once
+        cache = x.get("cache")
+        if cache is not None and cache.get("pack") is pk:
+            q0, q1 = cache["q"]
+        else:
+            t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)         # two roundings (mul, then add)
+            lw = pk["models"][0]
+            q0 = self._query(lw, tab[n0], t_root, R)
+            q1 = self._query(lw, tab[n1.reshape(-1).long()], t_hop1, R * N)
+            if cache is not None:
+                cache["pack"], cache["q"] = pk, (q0, q1)
+        h0 = self._attn_pass(pk, 0, None, None, R, N, n1, None, e1, dt1, n1, ew1, seg, q0)
+        h1 = self._attn_pass(pk, 0, None, None, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N, q1)
         return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg)
 
     # -------------------------------------------------------------- HIP training path (tm_tgat_attn_train_*)
@@ -448,25 +483,77 @@ class TGAT(nn.Module):
         B = emb.shape[0] // S
         return list(emb.split(B)) if B > 0 else [emb[:0]] * S
 
+    def prepare_contrast(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, subgraph_src, subgraph_tgt, subgraph_bgd):
+        """The inputs contrast derives from its batch (the three sides' roots and subgraphs concatenated in the
+        kernels' dtypes, the time offsets), built once: the training step's two contrasts of the same batch
+        (without and with explanation weights, temp_exp_main.py:597, :611) share them through
+        ``contrast(..., prepared=...)``.  The dict also keeps the queries of the first two passes once a contrast
+        has folded them (they depend on the batch and the frozen weights only)."""
+        dev = self._dev()
+        sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+        roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_idx_l, tgt_idx_l, bgd_idx_l)])
+
+        def cat(i, h, dtype):
+            xs = [sg[i][h] for sg in sgs]
+            if all(isinstance(x, torch.Tensor) and x.device == dev for x in xs):
+                # the three sides of a gathered pack are consecutive rows of one tensor: one view, and one
+                # dtype conversion instead of three (elementwise, so the same values as convert-then-cat)
+                return _as_dev(_cat_rows(xs), dev, dtype)
+            return torch.cat([_as_dev(x, dev, dtype) for x in xs])
+        x = self._prep_inputs([roots, cat(0, 0, torch.int32), cat(0, 1, torch.int32)],
+                              [cat(1, 0, torch.int32), cat(1, 1, torch.int32)],
+                              [cat(2, 0, torch.float64), cat(2, 1, torch.float64)], cut_time_l, n_segments=3)
+        x["cache"] = {}
+        return x
+
     # -------------------------------------------------------------- reference API
     def affinity(self, x1, x2):
         pk = self._pack()
         h = F.relu(F.linear(torch.cat([x1, x2], dim=1), pk["a1w"], pk["a1b"]))
         return F.linear(h, pk["a2w"], pk["a2b"])
 
+    def _score3(self, emb, live):
+        """(pos, neg) scores from the [3B, feat] embeddings of the segments src, tgt, bgd: [tgt; bgd] is emb's
+        tail (no copy).  ``live``: score with the live parameters (the HIP training path)."""
+        B = emb.shape[0] // 3
+        s, tb = emb.split([B, 2 * B])
+        score = (self.affinity_score if live else self.affinity)(torch.cat([s, s], dim=0), tb)
+        return score[:B], score[B:]
+
     def contrast(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, e_idx_l, subgraph_src, subgraph_tgt, subgraph_bgd,
-                 test=False, if_explain=False, exp_weights=None):
+                 test=False, if_explain=False, exp_weights=None, prepared=None, stacked_weights=None):
         """TGAT.py:461-481 -> (pos_score [B, 1], neg_score [B, 1]).  The three (or four) forward_msg calls
         run as segments of one launch per pass; the src side runs once when both pairs carry the same src
-        weights (the same objects, as temp_exp_main.py:613 builds them), twice otherwise."""
+        weights (the same objects, as temp_exp_main.py:613 builds them), twice otherwise.
+
+        ``prepared``: ``prepare_contrast``'s output for these same inputs (optional; shared by the contrasts of
+        one batch that run three segments).  ``stacked_weights=(hop-1 [3B, N], hop-2 [3B, N^2])``: the explanation
+        weights of the sides src, tgt, bgd as two tensors (what ``explain_groups`` returns), i.e.
+        ``exp_weights=[[s, t], [s, b]]`` of their per-side views without splitting and concatenating them;
+        implies ``if_explain``."""
         roots = [src_idx_l, tgt_idx_l, bgd_idx_l]
         sgs = [subgraph_src, subgraph_tgt, subgraph_bgd]
+        if stacked_weights is not None:
+            if exp_weights is not None:
+                raise ValueError("TGAT.contrast: give exp_weights or stacked_weights, not both")
+            ew1, ew2 = stacked_weights
+            x = prepared if prepared is not None else self.prepare_contrast(*roots, cut_time_l, *sgs)
+            if ew1.shape[0] != x["R"] or ew2.shape[0] != x["R"]:
+                raise ValueError(f"TGAT.contrast: stacked_weights need {x['R']} rows (src, tgt, bgd), got "
+                                 f"{tuple(ew1.shape)} and {tuple(ew2.shape)}")
+            return self._score3(self._embed(x, (ew1, ew2)), False)
         if not if_explain:
+            if prepared is not None:
+                return self._score3(self._embed(prepared), self._train_hip_ok())
             s, t, b = self._sides(roots, sgs, None, cut_time_l)
             s2 = s
         else:
             (w_s, w_t), (w_s2, w_b) = exp_weights[0], exp_weights[1]
             same = w_s is w_s2 or (len(w_s) == len(w_s2) and all(x is y for x, y in zip(w_s, w_s2)))
+            if same and prepared is not None:
+                dev = self._dev()
+                ew = [torch.cat([w[h].to(dev, torch.float32) for w in (w_s, w_t, w_b)]) for h in (0, 1)]
+                return self._score3(self._embed(prepared, ew), False)
             if same:
                 s, t, b = self._sides(roots, sgs, [w_s, w_t, w_b], cut_time_l)
                 s2 = s

@@ -14,6 +14,11 @@ autograd formulation (dropout and Beta ``rsample`` draw from torch's device RNG,
 step matches the reference statistically, not bit for bit; with ``Explainer.eval()`` and
 ``if_bern=False`` the step is deterministic and tests/test_gpu_train.py holds it to the reference).
 
+The base model is a TGN, a GraphMixer or a TGAT.  TGAT keeps the reference's per-side signature
+(``contrast(..., test=True, if_explain=True, exp_weights=[[src, tgt], [src, bgd]])``, temp_exp_main.py:609-616): the
+drivers hand it the stacked explanation pair as it is (``explained_contrast``, ``TGAT.contrast(stacked_weights=...)``)
+and dispatch on the base's class together with ``explainer.base_type`` (``base_is_tgat``).
+
 Data parallel: one process per GPU, each stepping its own whole batches; after
 backward the explainer's gradients (one flat fp32 bucket, ~0.46 MB at uslegis dims) are averaged
 with ONE all-reduce over RCCL before the optimizer step, so every rank keeps identical weights.  The
@@ -210,11 +215,46 @@ class GradAllReduce:
         self.finish()
 
 
+def base_is_tgat(explainer, base_model):
+    """True when the step runs on a TGAT base (per-side weights, ``test=`` / ``if_explain=`` arguments), False for the
+    bases that take ``explain_weights``.  The base's class and ``explainer.base_type`` must say the same; a mismatch
+    raises here, before any kernel reads a tensor of the wrong layout."""
+    from .tgat import TGAT
+    is_tgat = isinstance(base_model, TGAT)
+    if is_tgat != (explainer.base_type == "tgat"):
+        raise ValueError(f"explainer.base_type is {explainer.base_type!r} but the base model is a "
+                         f"{type(base_model).__name__}: build the explainer as TempME(base, "
+                         f"{'tgat' if is_tgat else 'tgn or graphmixer'!r}, ...) for this base")
+    return is_tgat
+
+
+def split_stacked_weights(ew1, ew2, flat=False):
+    """The stacked explanation weights (hop-1 [3B, N], hop-2 [3B, N^2], sides src, tgt, bgd) as TGAT's per-side
+    arguments, all views of the two tensors: ``exp_weights`` [[src, tgt], [src, bgd]] with every side a (hop-1 [B, N],
+    hop-2 [B, N^2]) pair (temp_exp_main.py:609-616), or with ``flat`` the 6-list [src0, src1, tgt0, tgt1, bgd0, bgd1]
+    of ``fidelity.threshold_test``'s tgat branch."""
+    B = int(ew1.shape[0]) // 3
+    if ew1.shape[0] != 3 * B or ew2.shape[0] != 3 * B:
+        raise ValueError(f"split_stacked_weights: need 3B rows in both tensors, got {tuple(ew1.shape)} and "
+                         f"{tuple(ew2.shape)}")
+    sides = [(ew1[s * B:(s + 1) * B], ew2[s * B:(s + 1) * B]) for s in range(3)]
+    if flat:
+        return [x for pair in sides for x in pair]
+    return [[sides[0], sides[1]], [sides[0], sides[2]]]
+
+
 def explain_sides(explainer, batch, imps, training):
     """Explainer.retrieve_explanation(sg_src, imp_src, walks_src, ..., training) (temp_exp_main.py:608-609);
     on the HIP path the three sides run as one explain_groups call.  Returns the reference's list
-    [hop-1 [3B, N], hop-2 [3B, N^2]] (hop-1 only for non-TGN bases)."""
+    [hop-1 [3B, N], hop-2 [3B, N^2]] for the bases that read both hops (``base_type`` "tgn" and "tgat": TGAT's
+    per-side pairs are views of the two, ``split_stacked_weights``), hop-1 only for the others."""
+    both = explainer.base_type in ("tgn", "tgat")
     if not explainer._hip_ok() or batch.stacked is None:
+        if explainer.base_type == "tgat":
+            # retrieve_explanation keeps hop-2 for a TGN base only: the per-side calls, concatenated
+            pairs = [explainer.retrieve_edge_imp_node(sg, g, w, training=training)
+                     for sg, g, w in zip(batch.subgraphs, imps, batch.walks)]
+            return [torch.cat([p[h] for p in pairs], dim=0) for h in (0, 1)]
         (sg_s, sg_t, sg_b), (w_s, w_t, w_b) = batch.subgraphs, batch.walks
         return explainer.retrieve_explanation(sg_s, imps[0], w_s, sg_t, imps[1], w_t, sg_b, imps[2], w_b,
                                               training=training)
@@ -232,22 +272,36 @@ def explain_sides(explainer, batch, imps, training):
     N = s1n.shape[-1]
     imp = _stacked_imp(batch, imps, G, B, W)
     e1, e2 = explainer.explain_groups(imp, eid3, ts3, s1n, s1e, s2n, s2e, G, B, W, N, training)
-    if explainer.base_type == "tgn":
+    if both:
         return [e1.reshape(G * B, N), e2.reshape(G * B, N * N)]
     return [e1.reshape(G * B, N)]
 
 
+def explained_contrast(base_model, batch, explanation, kw, tgat=False):
+    """The base model's contrast of ``batch`` with the explanation weights ``explain_sides`` returned; ``kw``:
+    ``prepare_step``'s keyword arguments (the prepared inputs).  A TGAT base (``tgat``) takes the stacked pair as
+    it is (``TGAT.contrast(stacked_weights=...)``: three segments, src computed once)."""
+    sg_s, sg_t, sg_b = batch.subgraphs
+    a = (batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, sg_s, sg_t, sg_b)
+    if tgat:
+        return base_model.contrast(*a, test=True, if_explain=True, stacked_weights=tuple(explanation), **kw)
+    return base_model.contrast(*a, explain_weights=explanation, **kw)
+
+
 def prepare_step(base_model, batch):
     """The explainer-independent part of a step (temp_exp_main.py:593-603): the base model's contrast
-    inputs (TGN: built once for both contrasts) and its original predictions -> y_ori, under no_grad.
+    inputs (TGN, TGAT: built once for both contrasts) and its original predictions -> y_ori, under no_grad.
     Issued for batch k+1 while batch k's gradient all-reduce is in flight (``train_step(overlap=...)``)."""
     kw = {}
     sg_s, sg_t, sg_b = batch.subgraphs
     with torch.no_grad():
         if hasattr(base_model, "prepare_contrast"):
             kw["prepared"] = base_model.prepare_contrast(batch.src, batch.dst, batch.fake, batch.ts, sg_s, sg_t, sg_b)
+        from .tgat import TGAT
+        # TGAT keeps the reference's signature (temp_exp_main.py:597-599)
+        ori = dict(kw, test=True, if_explain=False) if isinstance(base_model, TGAT) else kw
         pos_out_ori, neg_out_ori = base_model.contrast(batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx,
-                                                       sg_s, sg_t, sg_b, **kw)
+                                                       sg_s, sg_t, sg_b, **ori)
         y_pred = torch.cat([pos_out_ori, neg_out_ori], dim=0).sigmoid()
         y_ori = torch.where(y_pred > 0.5, 1., 0.).view(y_pred.size(0), 1)
     return kw, pos_out_ori, neg_out_ori, y_ori
@@ -275,7 +329,7 @@ def train_step(explainer, base_model, optimizer, batch, *, beta=0.5, prior_p=0.3
     the explainer) runs on this stream concurrently with the explainer's encoder and explanation, joined
     before the explained contrast."""
     criterion = criterion or torch.nn.BCEWithLogitsLoss()
-    sg_s, sg_t, sg_b = batch.subgraphs
+    tgat = base_is_tgat(explainer, base_model)
     w_s, w_t, w_b = batch.walks
     fork = prepared is None and side_stream is not None
     if fork:
@@ -294,8 +348,7 @@ def train_step(explainer, base_model, optimizer, batch, *, beta=0.5, prior_p=0.3
         if not torch.cuda.is_current_stream_capturing():
             # the side stream's allocations are read here: keep them from its pool until this stream is done
             _record_stream(prepared, cur)
-    pos_logit, neg_logit = base_model.contrast(batch.src, batch.dst, batch.fake, batch.ts, batch.e_idx, sg_s, sg_t,
-                                               sg_b, explain_weights=explanation, **kw)
+    pos_logit, neg_logit = explained_contrast(base_model, batch, explanation, kw, tgat)
     pred = torch.cat([pos_logit, neg_logit], dim=0)
     pred_loss = criterion(pred, y_ori)
     if batch.stacked is not None and explainer._hip_ok() and explainer.prior == "empirical":
@@ -485,3 +538,8 @@ def train_epoch(explainer, base_model, optimizer, buf, src, dst, ts, e_idx, bs, 
     if metrics and device_metrics:
         return steps_metrics_device(outs)
     return [step_metrics(o) for o in outs] if metrics else outs
+
+
+__all__ = ["Batch", "batch_from_pack", "encode_sides", "explain_sides", "explained_contrast", "base_is_tgat",
+           "split_stacked_weights", "prepare_step", "train_step", "run_steps", "GraphedTrainStep", "GradAllReduce",
+           "train_epoch", "epoch_spans", "step_metrics", "steps_metrics_device", "SIDES"]

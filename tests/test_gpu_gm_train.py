@@ -9,6 +9,7 @@ import torch
 
 import gm_train_ref as GR
 import tgn_inputs as TI
+from gm_shape_inputs import TRAIN
 from oracle import graphmixer_ref as O
 from tests.test_gpu_graphmixer import ATOL, CASES, RTOL
 from tests.test_graphmixer_oracle import SEEDS
@@ -18,6 +19,10 @@ pytestmark = pytest.mark.gpu
 # N, C, L, p, B: one / two token tiles, channel counts with and without padding to 16, a ragged last hidden chunk
 # (HC = 688 = 5 * 128 + 48), R N no multiple of any reduction chunk (B = 7), NULL masks (p = 0)
 SHAPES = [(30, 172, 3, 0.5, 20), (12, 172, 2, 0.5, 20), (20, 32, 1, 0.0, 20), (16, 100, 3, 0.5, 7), (20, 1, 3, 0.5, 20)]
+# every test below runs SHAPES (T = C, ids as before) and gm_shape_inputs.TRAIN (its own T: the fourth tile slot of
+# a wave at C > 192, T < C, 4 layers, N = 2 and 32)
+ALL_SHAPES = [(*s, None) for s in SHAPES] + [(N, C, L, p, B, T) for N, C, T, L, p, B in TRAIN]
+ALL_IDS = ["-".join(str(x) for x in s) for s in SHAPES] + [f"{N}-{C}-{L}-{p}-{B}-T{T}" for N, C, T, L, p, B in TRAIN]
 EMBED = ("projection_layer", "mlp_mixers")
 _cache = {}
 
@@ -42,17 +47,19 @@ def grads_of(model):
             if v.requires_grad}
 
 
-def make_case(dev, N, C, L, p, B):
+def make_case(dev, N, C, L, p, B, T=None):
     """Inputs as test_hip_ew_gradient_vs_oracle builds them (V = 300, E = 2000, padding neighbours at rate 0.25, one
     row with no valid neighbour); one HIP training step, a second identical one, the same call with the flag off,
-    and the fp64 / fp32 torch formulation with the same masks on the CPU.  Computed once per shape."""
-    key = (N, C, L, p, B)
+    and the fp64 / fp32 torch formulation with the same masks on the CPU.  T (default C) is the node-feature and
+    time-encoding width.  Computed once per shape."""
+    T = C if T is None else T
+    key = (N, C, L, p, B, T)
     if key in _cache:
         return _cache[key]
     from tempme_amd.graphmixer import GraphMixer
     rng = np.random.default_rng(N + C + L)
     V, E = 300, 2000
-    nf = rng.uniform(0, 1, (V, C)).astype(np.float32)
+    nf = rng.uniform(0, 1, (V, T)).astype(np.float32)
     ef = rng.uniform(0, 1, (E + 1, C)).astype(np.float32)
     nf[0] = ef[0] = 0
     torch.manual_seed(N + L)
@@ -114,25 +121,25 @@ def check_grads(grads, g64, g32, tag=""):
     return worst
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_logits_match_fp64_formulation(dev, N, C, L, p, B):
-    c = make_case(dev, N, C, L, p, B)
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_logits_match_fp64_formulation(dev, N, C, L, p, B, T):
+    c = make_case(dev, N, C, L, p, B, T)
     _, p64, n64, _ = c.ref64
     got = torch.cat([c.pos, c.neg]).double().cpu().numpy()
     print("max |logit - fp64|", float(np.abs(got - torch.cat([p64, n64]).numpy()).max()))
     np.testing.assert_allclose(got, torch.cat([p64, n64]).numpy(), atol=ATOL, rtol=RTOL)
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_parameter_gradients_match_fp64_formulation(dev, N, C, L, p, B):
-    c = make_case(dev, N, C, L, p, B)
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_parameter_gradients_match_fp64_formulation(dev, N, C, L, p, B, T):
+    c = make_case(dev, N, C, L, p, B, T)
     worst = check_grads(c.grads, c.ref64[3], c.ref32[3])
     print("worst err / bound per tensor kind:", {k: round(v, 4) for k, v in sorted(worst.items())})
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_every_embedding_parameter_has_a_gradient(dev, N, C, L, p, B):
-    c = make_case(dev, N, C, L, p, B)
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_every_embedding_parameter_has_a_gradient(dev, N, C, L, p, B, T):
+    c = make_case(dev, N, C, L, p, B, T)
     names = [k for k in c.grads if k.startswith(EMBED)]
     assert len(names) == 2 + 12 * L
     for k, g in c.grads.items():
@@ -140,17 +147,17 @@ def test_every_embedding_parameter_has_a_gradient(dev, N, C, L, p, B):
         assert g.shape == c.sd[k].shape
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_second_call_is_bitwise_equal(dev, N, C, L, p, B):
-    c = make_case(dev, N, C, L, p, B)
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_second_call_is_bitwise_equal(dev, N, C, L, p, B, T):
+    c = make_case(dev, N, C, L, p, B, T)
     assert torch.equal(c.pos, c.pos2) and torch.equal(c.neg, c.neg2)
     for k, g in c.grads.items():
         assert torch.equal(g, c.grads2[k]), k
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_path_markers(dev, N, C, L, p, B):
-    c = make_case(dev, N, C, L, p, B)
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_path_markers(dev, N, C, L, p, B, T):
+    c = make_case(dev, N, C, L, p, B, T)
     assert c.off_marker is None, "train_on_hip is off by default: the torch formulation must run"
     assert all(g is not None for g in c.off_grads.values())
     assert c.marker == (3 * B, N, p > 0), "the HIP training path did not run"
@@ -170,11 +177,11 @@ def test_path_markers(dev, N, C, L, p, B):
     m._gm_train_key = before
 
 
-@pytest.mark.parametrize("N,C,L,p,B", SHAPES)
-def test_eval_after_an_adam_step_follows_the_weights(dev, N, C, L, p, B):
+@pytest.mark.parametrize("N,C,L,p,B,T", ALL_SHAPES, ids=ALL_IDS)
+def test_eval_after_an_adam_step_follows_the_weights(dev, N, C, L, p, B, T):
     """One Adam step through the HIP path, then model.eval() under no_grad (the packed eval kernels) against the
     fp64 oracle on the updated state_dict: the packs follow the weights."""
-    c = make_case(dev, N, C, L, p, B)
+    c = make_case(dev, N, C, L, p, B, T)
     m = c.model
     try:
         opt = torch.optim.Adam(m.parameters(), lr=0.01)

@@ -2566,25 +2566,64 @@ extern "C" int tm_weights_free(tm_weights *w) {
 }
 
 extern "C" int64_t tm_encoder_workspace_bytes(const tm_weights *w, int64_t n_walks) {
-    (void)w;
-    return n_walks * 3 * 2 * (w ? w->h : HID) * (int64_t)sizeof(float) + (n_walks + 64) * (int64_t)sizeof(float) + 256;
+    return enc_ws_lay(w, n_walks).bytes;
+}
+// tm_encoder_pool_fwd: the partial rows follow; tm_encoder_pool_train_fwd: the same, F and the groups' std kept
+// for tm_encoder_pool_bwd
+extern "C" int64_t tm_encoder_pool_workspace_bytes(const tm_weights *w, int64_t n_walks) {
+    return enc_ws_lay(w, n_walks).pool_bytes;
+}
+extern "C" int64_t tm_encoder_pool_train_workspace_bytes(const tm_weights *w, int64_t n_walks) {
+    return enc_ws_lay(w, n_walks).pool_bytes;
 }
 
 static size_t gate_lds(const EncW &P) {
     return sizeof(float) * (TILE_ROWS * (r16(P.kdep) + 8) + TILE_ROWS * (r16(P.h) + 8) + TILE_ROWS * (r16(P.h / 2) + 8));
 }
 
+// ------------------------------------------------------------------ which kernels take these dims
+// lin_event's 16-wide K steps
+static int walk_nqe(const EncW &P) { return r16(P.kev) / 16; }
+// what every fused walk_kernel instance, and with it the table mode, asks of the dims: 11 node-feature tiles read as
+// float4, hid_dim 64, the category one-hot
+static bool walk_dims(const EncW &P) { return r16(P.dn) / 16 == 11 && P.dn % 4 == 0 && P.h == HID && P.cat; }
+// narrow edge features: 11..14 K steps, the edge row held in load_ef's EQ_MAX K steps
+static bool walk_narrow(const EncW &P) { return walk_nqe(P) >= 11 && walk_nqe(P) <= 14 && P.de <= 16 * EQ_MAX; }
+// wide edge features (e.g. BASELINE configs[4]: de = dn = 172): 21 or 22 K steps
+static bool walk_wide_steps(const EncW &P) { return (walk_nqe(P) == 21 || walk_nqe(P) == 22) && P.de > 16 * EQ_MAX; }
+// the register-resident gate kernels' packs (hid_dim 64)
+static bool gate_reg_dims(const EncW &P) { return P.d2.nq == 4 && P.d1.nt == 4 && P.d2.nt == 2; }
+
 // lin_event's K steps before the first one holding a count or time feature (= de / 16), when the
 // fused walk kernel has a table-mode instance for these dims (de = 32..47 with 11..14 K steps, as
-// Enron's 32; de = 160..175 with 21..22, as BASELINE configs[4]'s 172), else 0
+// Enron's 32; de = 160..175 with 21..22, as BASELINE configs[4]'s 172), else 0.
+// Two things differ from walk_pick on purpose.  The table's builder (launch_edge_tables) is gate_reg_kernel's
+// <13, 3, nqe> / <22, 11, nqe> form, so the table exists only where lin_event's and the gate's packs have that
+// form's shape (ev.nt, ev.nq, gate_reg_dims, d1.nq); the forward asks none of that of the gate, and checks
+// lin_event's pack in walk_layout_ok.  And the builder loads an edge row by element where de % 4 != 0, which the
+// forward's streamed rows cannot: at de = 165..175 off a multiple of 4 a table exists, and the forward runs the
+// unfused kernels, which do not read it.
 static int etab_q0(const EncW &P) {
-    const int nqe = r16(P.kev) / 16, ntd = r16(P.dn) / 16, q0 = P.de / 16;
-    if (P.h != HID || !P.cat) return 0;
-    if (ntd != 11 || P.dn % 4 || P.ev.nt != 11 || P.ev.nq != nqe || P.d1.nt != 4 || P.d2.nq != 4 || P.d2.nt != 2)
-        return 0;
-    if (q0 == 2 && nqe >= 11 && nqe <= 14 && P.d1.nq == 13) return 2;
-    if (q0 == 10 && (nqe == 21 || nqe == 22) && P.d1.nq == 22) return 10;
+    const int nqe = walk_nqe(P), q0 = P.de / 16;
+    if (!walk_dims(P) || P.ev.nt != 11 || P.ev.nq != nqe || !gate_reg_dims(P)) return 0;
+    if (q0 == 2 && walk_narrow(P) && P.d1.nq == 13) return 2;
+    if (q0 == 10 && walk_wide_steps(P) && P.d1.nq == 22) return 10;
     return 0;
+}
+
+// The fused walk kernel's instance for a forward: whether it takes these dims at all, and then walk_kernel<nqe, 11,
+// sef, q0, ., zn, ...> (launch_walk_pick).  `table`: the caller passed an edge table.
+struct WalkPick {
+    bool fused;
+    int nqe;
+    bool sef;   // streamed edge features: wide rows, one K step at a time (needs float4 rows), unless a table has them
+    int q0;     // table mode: lin_event starts at K step q0 (etab_q0), 0 without a table
+    bool zn;    // zero node features: one event_gcn branch; an instance exists with the narrow table only
+};
+static WalkPick walk_pick(const EncW &P, int node_zero, bool table) {
+    const bool wide = walk_wide_steps(P) && P.de % 4 == 0;
+    const int q0 = table ? etab_q0(P) : 0;
+    return {walk_dims(P) && (walk_narrow(P) || wide), walk_nqe(P), wide && q0 == 0, q0, q0 == 2 && node_zero != 0};
 }
 
 extern "C" int tm_edge_table_cols(const tm_weights *w) { return (w && etab_q0(w->P) > 0) ? 176 : 0; }
@@ -2594,13 +2633,37 @@ extern "C" int tm_edge_gate_table(const tm_weights *w, const tm_graph *g, const 
     return tm_edge_tables(w, g, e_feat, out_gf, nullptr, stream);
 }
 
+// gate_reg_kernel<nq> (nq = d1's K steps; the dims pass gate_reg_dims) on `blocks` workgroups, with the call
+// site's trailing arguments -- none: a table over edge ids; (nullptr, eid3, ts3): per walk position; then (list,
+// count, cache, n_cache): the listed positions only.  false, nothing launched: no instance for nq, and the caller
+// runs its LDS-tiled gate.
+static bool gate_reg_has(int nq) { return nq == 11 || nq == 12 || nq == 13 || nq == 22; }
+template <class... Rest>
+static bool launch_gate_reg(int nq, unsigned blocks, hipStream_t s, const EncW &P, int32_t n, const double *ets,
+                            const float *e_feat, float *out_gf, const Rest &...rest) {
+    if (nq == 11) gate_reg_kernel<11><<<dim3(blocks), 256, 0, s>>>(P, n, ets, e_feat, out_gf, rest...);
+    else if (nq == 12) gate_reg_kernel<12><<<dim3(blocks), 256, 0, s>>>(P, n, ets, e_feat, out_gf, rest...);
+    else if (nq == 13) gate_reg_kernel<13><<<dim3(blocks), 256, 0, s>>>(P, n, ets, e_feat, out_gf, rest...);
+    else if (nq == 22) gate_reg_kernel<22><<<dim3(blocks), 256, 0, s>>>(P, n, ets, e_feat, out_gf, rest...);
+    return gate_reg_has(nq);
+}
+// std_cut_gate_kernel<nq>, the drop-in's std + cache lookup whose workgroups compute the misses themselves; the
+// 22-wide key has no such instance (its misses are listed for gate_reg_kernel<22>)
+static bool std_cut_gate_has(int nq) { return nq == 11 || nq == 12 || nq == 13; }
+template <class... Args>
+static bool launch_std_cut_gate(int nq, dim3 grid, hipStream_t s, const Args &...args) {
+    if (nq == 11) std_cut_gate_kernel<11><<<grid, 1024, 0, s>>>(args...);
+    else if (nq == 12) std_cut_gate_kernel<12><<<grid, 1024, 0, s>>>(args...);
+    else if (nq == 13) std_cut_gate_kernel<13><<<grid, 1024, 0, s>>>(args...);
+    return std_cut_gate_has(nq);
+}
+
 // gate table (gf, needs the edge timestamps ets) and/or edge table (etab) over edge ids [0, n)
 static int launch_edge_tables(const tm_weights *w, int32_t n, const double *ets, const float *e_feat, float *out_gf,
                               float *out_etab, void *stream) {
     const int q0 = etab_q0(w->P);
     if (out_etab && q0 == 0) return fail(TM_E_UNSUPPORTED, "tm_edge_tables: no edge table for these encoder dims");
     hipEvent_t pe = prof_begin(S_(stream));
-    const int nq = w->P.d1.nq;
     const unsigned rblocks = (unsigned)((n + 63) / 64);
     if (out_etab) {   // one launch: gate table and edge table from the same edge-feature fragments
         const int nqe = w->P.ev.nq;
@@ -2610,14 +2673,7 @@ static int launch_edge_tables(const tm_weights *w, int32_t n, const double *ets,
         else if (q0 == 2) gate_reg_kernel<13, 3, 14><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf, out_etab);
         else if (nqe == 21) gate_reg_kernel<22, 11, 21><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf, out_etab);
         else gate_reg_kernel<22, 11, 22><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf, out_etab);
-    } else if (w->P.d2.nq == 4 && w->P.d1.nt == 4 && w->P.d2.nt == 2) {   // hid_dim 64: register-resident path
-        if (nq == 11) gate_reg_kernel<11><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf);
-        else if (nq == 12) gate_reg_kernel<12><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf);
-        else if (nq == 13) gate_reg_kernel<13><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf);
-        else if (nq == 22) gate_reg_kernel<22><<<dim3(rblocks), 256, 0, S_(stream)>>>(w->P, n, ets, e_feat, out_gf);
-        else gate_table_kernel<<<dim3((n + TILE_ROWS - 1) / TILE_ROWS), 256, gate_lds(w->P), S_(stream)>>>(
-            w->P, n, ets, e_feat, out_gf);
-    } else {
+    } else if (!(gate_reg_dims(w->P) && launch_gate_reg(w->P.d1.nq, rblocks, S_(stream), w->P, n, ets, e_feat, out_gf))) {
         gate_table_kernel<<<dim3((n + TILE_ROWS - 1) / TILE_ROWS), 256, gate_lds(w->P), S_(stream)>>>(w->P, n, ets,
                                                                                                     e_feat, out_gf);
     }
@@ -2650,8 +2706,7 @@ extern "C" int tm_edge_importance_tab(const float *gf, int32_t n_ids, int32_t n_
     if (rows == 0) return TM_OK;
     if (!gf || !eid3 || !imp || !sub1_node || !sub1_eid || !sub2_node || !sub2_eid || !out_h1 || !out_h2)
         return fail(TM_E_ARG, "tm_edge_importance_tab: NULL pointer");
-    int hbits = 6;
-    while ((1 << hbits) < 2 * 3 * W) ++hbits;
+    const int hbits = expl_hbits(W);
     if (hbits > 14) return fail(TM_E_UNSUPPORTED, "tm_edge_importance_tab: too many walks per event");
     hipEvent_t pe = prof_begin(S_(stream));
     explain_tab_kernel<<<dim3((unsigned)rows), EXPLAIN_TPB, 2 * sizeof(int32_t) * (1u << hbits), S_(stream)>>>(
@@ -2665,7 +2720,6 @@ static size_t gcn_lds(const EncW &P) {
     const int xsz = std::max(TILE_ROWS * (r16(P.kev) + 8), 2 * TILE_ROWS * (r16(P.h) + 8));
     return sizeof(float) * (xsz + 2 * TILE_ROWS * (r16(P.dn) + 8));
 }
-static size_t head_lds(const EncW &P, int tr) { return sizeof(float) * (4 * tr * (2 * P.h + 8)); }
 static void launch_gcn(const EncW &P, int node_zero, int64_t n_rows, size_t lds, const float *n_feat,
                        const float *e_feat, const int32_t *node6, const int32_t *eid3, const float *ts3, const float *cnt,
                        float *F, hipStream_t s) {
@@ -2674,21 +2728,14 @@ static void launch_gcn(const EncW &P, int node_zero, int64_t n_rows, size_t lds,
     else gcn_kernel<false><<<grid, 256, lds, s>>>(P, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, F);
 }
 
-// walks per head_kernel workgroup: 32 where the tiles fit the LDS, else 16
 // 16 walks per head_kernel workgroup (35 KB of LDS at hid_dim 64, four per CU; 32-walk ones hold two per CU
 // and measured 0-0.9 % slower per training step, profiles/r05_train_tiles_ab.txt)
-static int head_tr(const EncW &) { return 16; }
-static void launch_head(const EncW &P, int64_t n_walks, int64_t walks_per_group, int32_t W, const float *F,
-                        const float *ts3, const double *cut, const int32_t *cat, const float *stdv, float *out,
-                        const uint8_t *drop, float dscale, hipStream_t s) {
-    const int tr = head_tr(P);
-    if (tr == 32)
-        head_kernel<32><<<dim3((unsigned)((n_walks + 31) / 32)), 256, head_lds(P, 32), s>>>(
-            P, n_walks, walks_per_group, W, F, ts3, cut, cat, stdv, out, drop, dscale);
-    else
-        head_kernel<16><<<dim3((unsigned)((n_walks + 15) / 16)), 256, head_lds(P, 16), s>>>(
-            P, n_walks, walks_per_group, W, F, ts3, cut, cat, stdv, out, drop, dscale);
-}
+constexpr int HEAD_TR = 16;
+static size_t head_lds(const EncW &P) { return sizeof(float) * (4 * HEAD_TR * (2 * P.h + 8)); }
+// the measured 32-walk instance: nothing launches it; instantiated so that the code object keeps its kernel set
+template __global__ void tmk::head_kernel<32, false>(EncW, int64_t, int64_t, int32_t, const float *, const float *,
+                                                     const double *, const int32_t *, const float *, float *,
+                                                     const uint8_t *, float, const float *);
 
 // a grid of fewer units than this runs split (one wave per (unit, walk)): at most one round of resident
 // waves either way (1024 SIMDs x 2 waves), so the call's latency is the shorter pass chain
@@ -2696,7 +2743,7 @@ constexpr int64_t WALK_SPLIT_UNITS = 512;
 
 static bool walk_split(int64_t units, int32_t M) { return units * M <= 3 * WALK_SPLIT_UNITS && units < WALK_SPLIT_UNITS; }
 
-// a.ticket zeroed on the stream before the launch unless walk_split (encoder_fwd_impl)
+// a.ticket zeroed on the stream before the launch unless walk_split (encoder_forward)
 template <int NQE, bool SEF, int Q0, bool ZN, bool POOL, bool PAIR>
 static void launch_walk_as(const WalkArgs &a, hipStream_t s) {
     const int64_t units = (a.n_slots + 15) / 16;
@@ -2732,12 +2779,154 @@ static void launch_walk_as(const WalkArgs &a, hipStream_t s) {
 
 // the zero-node table-mode instances run the pair pass unless tm_debug_set(TM_DEBUG_WALK_SINGLE, 1) asks for the
 // single-position pass (tests compare the two bit for bit)
-template <int NQE, bool SEF = false, int Q0 = 0, bool ZN = false, bool POOL = false>
+template <int NQE, bool SEF, int Q0, bool ZN, bool POOL>
 static void launch_walk(const WalkArgs &a, hipStream_t s) {
     if constexpr (ZN && Q0 > 0 && !SEF && !POOL) {
         if (!debug_opt(TM_DEBUG_WALK_SINGLE)) return launch_walk_as<NQE, SEF, Q0, ZN, POOL, true>(a, s);
     }
     launch_walk_as<NQE, SEF, Q0, ZN, POOL, false>(a, s);
+}
+
+// The walk_kernel instance table: every instance the library has, once, for the plain (POOL = false) and the
+// pooled forward.  k.fused holds (walk_pick), so nqe is 11..14 unless the features are wide (21 or 22).
+template <bool POOL>
+static void launch_walk_pick(const WalkPick &k, const WalkArgs &a, hipStream_t s) {
+    const int nqe = k.nqe;
+    if (k.zn) {   // edge table, zero node features: one event_gcn branch (ZN)
+        if (nqe == 11) launch_walk<11, false, 2, true, POOL>(a, s);
+        else if (nqe == 12) launch_walk<12, false, 2, true, POOL>(a, s);
+        else if (nqe == 13) launch_walk<13, false, 2, true, POOL>(a, s);
+        else launch_walk<14, false, 2, true, POOL>(a, s);
+    } else if (k.q0 == 2) {   // edge table: lin_event from K step 2
+        if (nqe == 11) launch_walk<11, false, 2, false, POOL>(a, s);
+        else if (nqe == 12) launch_walk<12, false, 2, false, POOL>(a, s);
+        else if (nqe == 13) launch_walk<13, false, 2, false, POOL>(a, s);
+        else launch_walk<14, false, 2, false, POOL>(a, s);
+    } else if (k.q0 == 10) {   // edge table: lin_event from K step 10 (no streamed edge features)
+        if (nqe == 21) launch_walk<21, false, 10, false, POOL>(a, s);
+        else launch_walk<22, false, 10, false, POOL>(a, s);
+    } else if (k.sef) {   // wide edge features, streamed per K step
+        if (nqe == 21) launch_walk<21, true, 0, false, POOL>(a, s);
+        else launch_walk<22, true, 0, false, POOL>(a, s);
+    } else if (nqe == 11) launch_walk<11, false, 0, false, POOL>(a, s);
+    else if (nqe == 12) launch_walk<12, false, 0, false, POOL>(a, s);
+    else if (nqe == 13) launch_walk<13, false, 0, false, POOL>(a, s);
+    else launch_walk<14, false, 0, false, POOL>(a, s);
+}
+
+// ------------------------------------------------------------------ the encoder forwards
+// One forward: the arguments of tm_encoder_fwd_tab, and what the other three entry points add to them.
+struct EncFwd {
+    const char *who, *who_tab;   // the entry point named in messages; the one named where it refuses a table
+    const tm_weights *w;
+    const float *n_feat, *e_feat, *etab;
+    int32_t n_groups, B, W, M;
+    const int32_t *node6, *eid3;
+    const float *ts3;
+    const int32_t *cat;
+    const double *cut;
+    const float *cnt;
+    void *workspace;
+    float *out;
+    void *stream;
+    // false: the groups' std values are already in the workspace (tm_dropin_forward's std_cut_kernel)
+    bool do_std = true;
+    // training (explainer_new.py:174-201 with dropout active): never the fused kernel -- F [n_walks * 3][2h] and the
+    // groups' std stay in the workspace for the backward -- and event_gcn's register-resident form where the dims
+    // have one; keep-masks nullable
+    bool train = false;
+    const uint8_t *drop = nullptr;
+    float dscale = 1.f;
+    // pooled (enhance_predict_walks, :221-258): the kernels end at attention.MLP's hidden layer, weighted by wgt,
+    // as partial rows in the workspace; pool_tail_kernel sums them per event into out [n_events][ld_out]
+    bool pool = false;
+    const float *wgt = nullptr;
+    int64_t ld_out = 0;
+};
+
+static int refuse(int code, const char *who, const char *what) { return fail(code, std::string(who) + ": " + what); }
+
+// the LDS-tiled kernels: gcn_kernel fills F, head_kernel<16[, POOL]> reads it
+static int launch_tiled(const EncFwd &c, const EncWs &ws, int64_t n_walks, hipStream_t s) {
+    const EncW &P = c.w->P;
+    const int nz = c.w->node_zero;
+    hipEvent_t pe = prof_begin(s);
+    if (!(c.train && launch_gcn_fwd_reg(P, nz, n_walks * 3, c.n_feat, c.e_feat, c.node6, c.eid3, c.ts3, c.cnt, ws.F, s)))
+        launch_gcn(P, nz, n_walks * 3, gcn_lds(P), c.n_feat, c.e_feat, c.node6, c.eid3, c.ts3, c.cnt, ws.F, s);
+    TM_CHECK_LAUNCH();
+    prof_end("gcn_kernel", s, pe);
+    pe = prof_begin(s);
+    const dim3 grid((unsigned)((n_walks + HEAD_TR - 1) / HEAD_TR));
+    if (c.pool)
+        head_kernel<HEAD_TR, true><<<grid, 256, head_lds(P), s>>>(P, n_walks, (int64_t)c.B * c.W, c.W, ws.F, c.ts3, c.cut,
+                                                                  c.cat, ws.stdv, ws.part, c.drop, c.dscale, c.wgt);
+    else
+        head_kernel<HEAD_TR><<<grid, 256, head_lds(P), s>>>(P, n_walks, (int64_t)c.B * c.W, c.W, ws.F, c.ts3, c.cut, c.cat,
+                                                            ws.stdv, c.out, c.drop, c.dscale);
+    TM_CHECK_LAUNCH();
+    prof_end(!c.pool ? "head_kernel" : c.train ? "head_pool_train_kernel" : "head_pool_kernel", s, pe);
+    return TM_OK;
+}
+
+// validate, carve the workspace, the groups' std, the fused kernel or the tiled pair, the pool tail
+static int encoder_forward(const EncFwd &c) {
+    if (!c.w || c.n_groups < 0 || c.B < 0 || c.W < 0 || c.M <= 0) return refuse(TM_E_ARG, c.who, "bad arguments");
+    if (c.W % c.M) return refuse(TM_E_SHAPE, c.who, "W must be a multiple of M (walks per hop-1 slot)");
+    const int64_t n_events = (int64_t)c.n_groups * c.B, n_walks = n_events * c.W;
+    if ((c.pool ? n_events : n_walks) == 0) return TM_OK;
+    const EncW &P = c.w->P;
+    if (c.pool && c.ld_out < P.hm) return refuse(TM_E_ARG, c.who, "ld_out below the row width (hid_dim (+ 12))");
+    if (!c.n_feat || !c.e_feat || !c.node6 || !c.eid3 || !c.ts3 || !c.cat || !c.cut || !c.cnt || !c.workspace ||
+        !c.out || (c.pool && !c.wgt))
+        return refuse(TM_E_ARG, c.who, "NULL pointer");
+    // (the pooled training forward is the one that also asks about its head tile)
+    if (gcn_lds(P) > 160 * 1024 || (c.pool && c.train && (head_lds(P) > 160 * 1024 || P.h > 256)))
+        return refuse(TM_E_UNSUPPORTED, c.who, "feature dims too large for LDS tile");
+    hipStream_t s = S_(c.stream);
+    const EncWs ws = enc_ws(c.w, n_walks, c.workspace);
+    int32_t n_part = c.W;   // pooled: partial rows per event
+    if (n_walks > 0) {
+        if (c.do_std) {
+            hipEvent_t pe = prof_begin(s);
+            if (P.tg) std_kernel<<<dim3(c.n_groups), 1024, 0, s>>>(c.B, c.W, c.cut, c.ts3, ws.stdv);
+            TM_CHECK_LAUNCH();
+            prof_end("std_kernel", s, pe);
+        }
+        const WalkPick k = walk_pick(P, c.w->node_zero, c.etab != nullptr);
+        if (c.etab && k.q0 == 0) return refuse(TM_E_UNSUPPORTED, c.who_tab, "no edge table for these dims");
+        if (k.fused && !c.train) {   // fused register-resident path
+            if (!walk_layout_ok(P, k.nqe)) return refuse(TM_E_UNSUPPORTED, c.who, "weight layout mismatch");
+            const int64_t n_slots = n_walks / c.M, units = (n_slots + 15) / 16;
+            WalkArgs a{P,     n_slots, c.W,     c.M,   c.B * c.W, c.n_feat, c.e_feat,  c.node6, c.eid3, c.cat,
+                       c.ts3, c.cnt,   ws.stdv, c.cut, c.pool ? ws.part : c.out,       c.etab,  ws.ticket, c.wgt};
+            const bool split = walk_split(units, c.M);
+            if (!split) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
+            if (c.pool) n_part = split ? c.W : c.W / c.M;
+            hipEvent_t pe = prof_begin(s);
+            if (c.pool) launch_walk_pick<true>(k, a, s);
+            else launch_walk_pick<false>(k, a, s);
+            TM_CHECK_LAUNCH();
+            prof_end(c.pool ? "walk_pool_kernel" : "walk_kernel", s, pe);
+        } else if (int rc = launch_tiled(c, ws, n_walks, s)) {
+            return rc;
+        }
+    }
+    if (c.pool) {
+        hipEvent_t pe = prof_begin(s);
+        launch_pool_tail(P.a2, n_events, c.W, n_part, P.h, P.cat, ws.part, c.wgt, c.cat, c.out, c.ld_out, s);
+        TM_CHECK_LAUNCH();
+        prof_end("pool_tail_kernel", s, pe);
+    }
+    return TM_OK;
+}
+
+extern "C" int tm_encoder_fwd_tab(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
+                                  int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6,
+                                  const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
+                                  const float *cnt, void *workspace, float *out_imp, void *stream) {
+    // its checks are tm_encoder_fwd's and carry that name; its own stands where the table is refused
+    return encoder_forward({"tm_encoder_fwd", "tm_encoder_fwd_tab", w, n_feat, e_feat, etab, n_groups, B, W, M, node6,
+                            eid3, ts3, cat, cut, cnt, workspace, out_imp, stream});
 }
 
 extern "C" int tm_encoder_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
@@ -2748,278 +2937,39 @@ extern "C" int tm_encoder_fwd(const tm_weights *w, const float *n_feat, const fl
                               workspace, out_imp, stream);
 }
 
-static int encoder_fwd_impl(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
-                            int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6, const int32_t *eid3,
-                            const float *ts3, const int32_t *cat, const double *cut, const float *cnt, void *workspace,
-                            float *out_imp, void *stream, bool do_std);
-
-extern "C" int tm_encoder_fwd_tab(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
-                                  int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6,
-                                  const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
-                                  const float *cnt, void *workspace, float *out_imp, void *stream) {
-    return encoder_fwd_impl(w, n_feat, e_feat, etab, n_groups, B, W, M, node6, eid3, ts3, cat, cut, cnt, workspace,
-                            out_imp, stream, true);
-}
-
-// the encoder launches; do_std = false: the groups' std values are already in the workspace (std_cut_kernel)
-static int encoder_fwd_impl(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
-                            int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6, const int32_t *eid3,
-                            const float *ts3, const int32_t *cat, const double *cut, const float *cnt, void *workspace,
-                            float *out_imp, void *stream, bool do_std) {
-    if (!w || n_groups < 0 || B < 0 || W < 0 || M <= 0) return fail(TM_E_ARG, "tm_encoder_fwd: bad arguments");
-    if (W % M) return fail(TM_E_SHAPE, "tm_encoder_fwd: W must be a multiple of M (walks per hop-1 slot)");
-    const int64_t n_walks = (int64_t)n_groups * B * W;
-    if (n_walks == 0) return TM_OK;
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !workspace || !out_imp)
-        return fail(TM_E_ARG, "tm_encoder_fwd: NULL pointer");
-    const EncW &P = w->P;
-    const size_t lds_g = gcn_lds(P);
-    if (lds_g > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_fwd: feature dims too large for LDS tile");
-    hipStream_t s = S_(stream);
-    float *F = reinterpret_cast<float *>(workspace);
-    float *stdv = F + n_walks * 3 * 2 * P.h;
-    hipEvent_t pe = nullptr;
-    if (do_std) {
-        pe = prof_begin(s);
-        if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
-        TM_CHECK_LAUNCH();
-        prof_end("std_kernel", s, pe);
-    }
-    if (etab && etab_q0(P) == 0) return fail(TM_E_UNSUPPORTED, "tm_encoder_fwd_tab: no edge table for these dims");
-    const int nqe = r16(P.kev) / 16, ntd = r16(P.dn) / 16;
-    const bool narrow = nqe >= 11 && nqe <= 14 && P.de <= 16 * EQ_MAX;
-    // wide edge features (e.g. BASELINE configs[4]: de = dn = 172): streamed per K step
-    const bool wide = (nqe == 21 || nqe == 22) && P.de > 16 * EQ_MAX && P.de % 4 == 0;
-    if (ntd == 11 && P.dn % 4 == 0 && (narrow || wide) && P.h == HID && P.cat) {
-        // fused register-resident path
-        if (!walk_layout_ok(P, nqe)) return fail(TM_E_UNSUPPORTED, "tm_encoder_fwd: weight layout mismatch");
-        const int64_t n_slots = n_walks / M;
-        const int64_t units = (n_slots + 15) / 16;
-        // the unit counter of a dynamic persistent launch lives in the workspace's F region (unused by this path)
-        WalkArgs a{P, n_slots, W, M, B * W, n_feat, e_feat, node6, eid3, cat, ts3, cnt, stdv, cut, out_imp, etab,
-                   reinterpret_cast<uint32_t *>(F)};
-        const int q0 = etab ? etab_q0(P) : 0;
-        if (!walk_split(units, M)) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
-        pe = prof_begin(s);
-        if (q0 == 2 && w->node_zero) {   // edge table, zero node features: one event_gcn branch (ZN)
-            if (nqe == 11) launch_walk<11, false, 2, true>(a, s);
-            else if (nqe == 12) launch_walk<12, false, 2, true>(a, s);
-            else if (nqe == 13) launch_walk<13, false, 2, true>(a, s);
-            else launch_walk<14, false, 2, true>(a, s);
-        } else if (q0 == 2) {        // edge table: lin_event from K step 2
-            if (nqe == 11) launch_walk<11, false, 2>(a, s);
-            else if (nqe == 12) launch_walk<12, false, 2>(a, s);
-            else if (nqe == 13) launch_walk<13, false, 2>(a, s);
-            else launch_walk<14, false, 2>(a, s);
-        } else if (q0 == 10) {   // edge table: lin_event from K step 10 (no streamed edge features)
-            if (nqe == 21) launch_walk<21, false, 10>(a, s);
-            else launch_walk<22, false, 10>(a, s);
-        } else if (wide) {
-            if (nqe == 21) launch_walk<21, true>(a, s);
-            else launch_walk<22, true>(a, s);
-        } else if (nqe == 11) launch_walk<11>(a, s);
-        else if (nqe == 12) launch_walk<12>(a, s);
-        else if (nqe == 13) launch_walk<13>(a, s);
-        else launch_walk<14>(a, s);
-        TM_CHECK_LAUNCH();
-        prof_end("walk_kernel", s, pe);
-        return TM_OK;
-    }
-    const int64_t n_rows = n_walks * 3;
-    pe = prof_begin(s);
-    launch_gcn(P, w->node_zero, n_rows, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
-    TM_CHECK_LAUNCH();
-    prof_end("gcn_kernel", s, pe);
-    pe = prof_begin(s);
-    launch_head(P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, out_imp, nullptr, 1.f, s);
-    TM_CHECK_LAUNCH();
-    prof_end("head_kernel", s, pe);
-    return TM_OK;
-}
-
-// ------------------------------------------------------------------ pooled encoder (enhance_predict_walks)
-// the workspace of tm_encoder_pool_fwd: tm_encoder_fwd's (F, the groups' std, the unit counter), then the
-// partials [n_walks][h] (the fused kernel uses n_slots * PM <= n_walks rows of them)
-static int64_t pool_part_offset(const tm_weights *w, int64_t n_walks) {
-    return (tm_encoder_workspace_bytes(w, n_walks) + 255) & ~(int64_t)255;
-}
-
-extern "C" int64_t tm_encoder_pool_workspace_bytes(const tm_weights *w, int64_t n_walks) {
-    return pool_part_offset(w, n_walks) + n_walks * (w ? w->h : HID) * (int64_t)sizeof(float) + 256;
-}
-
-// the fused kernel's POOL instance for these dims (the instance table of encoder_fwd_impl)
-static void launch_walk_pool(const WalkArgs &a, int nqe, bool wide, int q0, int node_zero, hipStream_t s) {
-    if (q0 == 2 && node_zero) {
-        if (nqe == 11) launch_walk<11, false, 2, true, true>(a, s);
-        else if (nqe == 12) launch_walk<12, false, 2, true, true>(a, s);
-        else if (nqe == 13) launch_walk<13, false, 2, true, true>(a, s);
-        else launch_walk<14, false, 2, true, true>(a, s);
-    } else if (q0 == 2) {
-        if (nqe == 11) launch_walk<11, false, 2, false, true>(a, s);
-        else if (nqe == 12) launch_walk<12, false, 2, false, true>(a, s);
-        else if (nqe == 13) launch_walk<13, false, 2, false, true>(a, s);
-        else launch_walk<14, false, 2, false, true>(a, s);
-    } else if (q0 == 10) {
-        if (nqe == 21) launch_walk<21, false, 10, false, true>(a, s);
-        else launch_walk<22, false, 10, false, true>(a, s);
-    } else if (wide) {
-        if (nqe == 21) launch_walk<21, true, 0, false, true>(a, s);
-        else launch_walk<22, true, 0, false, true>(a, s);
-    } else if (nqe == 11) launch_walk<11, false, 0, false, true>(a, s);
-    else if (nqe == 12) launch_walk<12, false, 0, false, true>(a, s);
-    else if (nqe == 13) launch_walk<13, false, 0, false, true>(a, s);
-    else launch_walk<14, false, 0, false, true>(a, s);
-}
-
 extern "C" int tm_encoder_pool_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, const float *etab,
                                    int32_t n_groups, int32_t B, int32_t W, int32_t M, const int32_t *node6,
                                    const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
                                    const float *cnt, const float *wgt, void *workspace, float *out, int64_t ld_out,
                                    void *stream) {
-    if (!w || n_groups < 0 || B < 0 || W < 0 || M <= 0) return fail(TM_E_ARG, "tm_encoder_pool_fwd: bad arguments");
-    if (W % M) return fail(TM_E_SHAPE, "tm_encoder_pool_fwd: W must be a multiple of M (walks per hop-1 slot)");
-    const int64_t n_walks = (int64_t)n_groups * B * W, n_events = (int64_t)n_groups * B;
-    if (n_events == 0) return TM_OK;
-    const EncW &P = w->P;
-    if (ld_out < P.hm) return fail(TM_E_ARG, "tm_encoder_pool_fwd: ld_out below the row width (hid_dim (+ 12))");
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !out)
-        return fail(TM_E_ARG, "tm_encoder_pool_fwd: NULL pointer");
-    const size_t lds_g = gcn_lds(P);
-    if (lds_g > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: feature dims too large for LDS tile");
-    hipStream_t s = S_(stream);
-    float *F = reinterpret_cast<float *>(workspace);
-    float *stdv = F + n_walks * 3 * 2 * P.h;
-    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + pool_part_offset(w, n_walks));
-    int32_t n_part = W;                                   // partial rows per event
-    if (n_walks > 0) {
-        hipEvent_t pe = prof_begin(s);
-        if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
-        TM_CHECK_LAUNCH();
-        prof_end("std_kernel", s, pe);
-        if (etab && etab_q0(P) == 0) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: no edge table for these dims");
-        const int nqe = r16(P.kev) / 16, ntd = r16(P.dn) / 16;
-        const bool narrow = nqe >= 11 && nqe <= 14 && P.de <= 16 * EQ_MAX;
-        const bool wide = (nqe == 21 || nqe == 22) && P.de > 16 * EQ_MAX && P.de % 4 == 0;
-        if (ntd == 11 && P.dn % 4 == 0 && (narrow || wide) && P.h == HID && P.cat) {
-            if (!walk_layout_ok(P, nqe)) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_fwd: weight layout mismatch");
-            const int64_t n_slots = n_walks / M;
-            const int64_t units = (n_slots + 15) / 16;
-            WalkArgs a{P, n_slots, W, M, B * W, n_feat, e_feat, node6, eid3, cat, ts3, cnt, stdv, cut, part, etab,
-                       reinterpret_cast<uint32_t *>(F), wgt};
-            const bool split = walk_split(units, M);
-            if (!split) TM_HIP(hipMemsetAsync(a.ticket, 0, sizeof(uint32_t), s));
-            n_part = split ? W : W / M;
-            pe = prof_begin(s);
-            launch_walk_pool(a, nqe, wide, etab ? etab_q0(P) : 0, w->node_zero, s);
-            TM_CHECK_LAUNCH();
-            prof_end("walk_pool_kernel", s, pe);
-        } else {
-            pe = prof_begin(s);
-            launch_gcn(P, w->node_zero, n_walks * 3, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
-            TM_CHECK_LAUNCH();
-            prof_end("gcn_kernel", s, pe);
-            pe = prof_begin(s);
-            head_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, head_lds(P, 16), s>>>(
-                P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, part, nullptr, 1.f, wgt);
-            TM_CHECK_LAUNCH();
-            prof_end("head_pool_kernel", s, pe);
-        }
-    }
-    hipEvent_t pe = prof_begin(s);
-    launch_pool_tail(P.a2, n_events, W, n_part, P.h, P.cat, part, wgt, cat, out, ld_out, s);
-    TM_CHECK_LAUNCH();
-    prof_end("pool_tail_kernel", s, pe);
-    return TM_OK;
+    EncFwd c{"tm_encoder_pool_fwd", "tm_encoder_pool_fwd", w, n_feat, e_feat, etab, n_groups, B, W, M, node6, eid3, ts3,
+             cat, cut, cnt, workspace, out, stream};
+    c.pool = true, c.wgt = wgt, c.ld_out = ld_out;
+    return encoder_forward(c);
 }
 
-// Training forward (explainer_new.py:174-201 with dropout active): the LDS-tiled kernels, keeping
-// F [n_walks*3, 2h] and the per-group std in `workspace` for tm_encoder_bwd.  drop nullable (eval).
 extern "C" int tm_encoder_train_fwd(const tm_weights *w, const float *n_feat, const float *e_feat, int32_t n_groups,
                                     int32_t B, int32_t W, const int32_t *node6, const int32_t *eid3, const float *ts3,
                                     const int32_t *cat, const double *cut, const float *cnt, const uint8_t *drop,
                                     float drop_scale, void *workspace, float *out_imp, void *stream) {
-    if (!w || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_train_fwd: bad arguments");
-    const int64_t n_walks = (int64_t)n_groups * B * W;
-    if (n_walks == 0) return TM_OK;
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !workspace || !out_imp)
-        return fail(TM_E_ARG, "tm_encoder_train_fwd: NULL pointer");
-    const EncW &P = w->P;
-    const size_t lds_g = gcn_lds(P);
-    if (lds_g > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_train_fwd: feature dims too large for LDS tile");
-    hipStream_t s = S_(stream);
-    float *F = reinterpret_cast<float *>(workspace);
-    float *stdv = F + n_walks * 3 * 2 * P.h;
-    hipEvent_t pe = prof_begin(s);
-    if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
-    TM_CHECK_LAUNCH();
-    prof_end("std_kernel", s, pe);
-    const int64_t n_rows = n_walks * 3;
-    pe = prof_begin(s);
-    if (!launch_gcn_fwd_reg(P, w->node_zero, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, F, s))
-        launch_gcn(P, w->node_zero, n_rows, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
-    TM_CHECK_LAUNCH();
-    prof_end("gcn_kernel", s, pe);
-    pe = prof_begin(s);
-    launch_head(P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, out_imp, drop, drop_scale, s);
-    TM_CHECK_LAUNCH();
-    prof_end("head_kernel", s, pe);
-    return TM_OK;
+    EncFwd c{"tm_encoder_train_fwd", "", w, n_feat, e_feat, nullptr, n_groups, B, W, 1, node6, eid3, ts3, cat, cut, cnt,
+             workspace, out_imp, stream};
+    c.train = true, c.drop = drop, c.dscale = drop_scale;
+    return encoder_forward(c);
 }
 
-// the workspace of tm_encoder_pool_train_fwd: tm_encoder_train_fwd's (F and the groups' std, kept for
-// tm_encoder_pool_bwd), then the per-walk partial rows [n_walks][h]
-extern "C" int64_t tm_encoder_pool_train_workspace_bytes(const tm_weights *w, int64_t n_walks) {
-    return pool_part_offset(w, n_walks) + n_walks * (w ? w->h : HID) * (int64_t)sizeof(float) + 256;
-}
-
-// Training forward of the pooled encoder (enhance_predict_walks under autograd, explainer_new.py:221-258): the
-// LDS-tiled kernels of tm_encoder_train_fwd up to attention.MLP's hidden layer (both dropouts of the attention
-// applied in the head), then the per-event tail of tm_encoder_pool_fwd.  F and the per-group std stay in
-// `workspace` for tm_encoder_pool_bwd.
+// the training forward up to attention.MLP's hidden layer (both dropouts of the attention applied in the head), then
+// the per-event tail of tm_encoder_pool_fwd
 extern "C" int tm_encoder_pool_train_fwd(const tm_weights *w, const float *n_feat, const float *e_feat,
                                          int32_t n_groups, int32_t B, int32_t W, const int32_t *node6,
                                          const int32_t *eid3, const float *ts3, const int32_t *cat, const double *cut,
                                          const float *cnt, const float *wgt, const uint8_t *drop, float drop_scale,
                                          void *workspace, float *out, int64_t ld_out, void *stream) {
-    if (!w || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: bad arguments");
-    const int64_t n_walks = (int64_t)n_groups * B * W, n_events = (int64_t)n_groups * B;
-    if (n_events == 0) return TM_OK;
-    const EncW &P = w->P;
-    if (ld_out < P.hm)
-        return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: ld_out below the row width (hid_dim (+ 12))");
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !out)
-        return fail(TM_E_ARG, "tm_encoder_pool_train_fwd: NULL pointer");
-    const size_t lds_g = gcn_lds(P);
-    if (lds_g > 160 * 1024 || head_lds(P, 16) > 160 * 1024 || P.h > 256)
-        return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_train_fwd: feature dims too large for LDS tile");
-    hipStream_t s = S_(stream);
-    float *F = reinterpret_cast<float *>(workspace);
-    float *stdv = F + n_walks * 3 * 2 * P.h;
-    float *part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + pool_part_offset(w, n_walks));
-    hipEvent_t pe = nullptr;
-    if (n_walks > 0) {
-        pe = prof_begin(s);
-        if (P.tg) std_kernel<<<dim3(n_groups), 1024, 0, s>>>(B, W, cut, ts3, stdv);
-        TM_CHECK_LAUNCH();
-        prof_end("std_kernel", s, pe);
-        const int64_t n_rows = n_walks * 3;
-        pe = prof_begin(s);
-        if (!launch_gcn_fwd_reg(P, w->node_zero, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, F, s))
-            launch_gcn(P, w->node_zero, n_rows, lds_g, n_feat, e_feat, node6, eid3, ts3, cnt, F, s);
-        TM_CHECK_LAUNCH();
-        prof_end("gcn_kernel", s, pe);
-        pe = prof_begin(s);
-        head_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, head_lds(P, 16), s>>>(
-            P, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, part, drop, drop_scale, wgt);
-        TM_CHECK_LAUNCH();
-        prof_end("head_pool_train_kernel", s, pe);
-    }
-    pe = prof_begin(s);
-    launch_pool_tail(P.a2, n_events, W, W, P.h, P.cat, part, wgt, cat, out, ld_out, s);
-    TM_CHECK_LAUNCH();
-    prof_end("pool_tail_kernel", s, pe);
-    return TM_OK;
+    EncFwd c{"tm_encoder_pool_train_fwd", "", w, n_feat, e_feat, nullptr, n_groups, B, W, 1, node6, eid3, ts3, cat, cut,
+             cnt, workspace, out, stream};
+    c.train = true, c.drop = drop, c.dscale = drop_scale;
+    c.pool = true, c.wgt = wgt, c.ld_out = ld_out;
+    return encoder_forward(c);
 }
 
 extern "C" int tm_edge_importance(const tm_weights *w, const float *e_feat, int32_t n_groups, int32_t B, int32_t W,
@@ -3031,8 +2981,7 @@ extern "C" int tm_edge_importance(const tm_weights *w, const float *e_feat, int3
     if (rows == 0) return TM_OK;
     if (!e_feat || !eid3 || !ts3 || !imp || !sub1_node || !sub1_eid || !sub2_node || !sub2_eid || !out_h1 || !out_h2)
         return fail(TM_E_ARG, "tm_edge_importance: NULL pointer");
-    int hbits = 6;
-    while ((1 << hbits) < 2 * 3 * W) ++hbits;
+    const int hbits = expl_hbits(W);
     if (hbits > 14) return fail(TM_E_UNSUPPORTED, "tm_edge_importance: too many walks per event");
     const EncW &P = w->P;
     const size_t lds = gate_lds(P);
@@ -3247,8 +3196,7 @@ extern "C" int tm_dropin_forward(tm_dropin *d, int32_t k, int32_t sync, const tm
     const EncW &P = w->P;
     const int64_t n_pos = n_walks * 3;
     const int nq = P.d1.nq;
-    const bool reg = out_gfac && P.dep && P.d2.nq == 4 && P.d1.nt == 4 && P.d2.nt == 2 && n_pos < INT32_MAX &&
-                     (nq == 11 || nq == 12 || nq == 13 || nq == 22);
+    const bool reg = out_gfac && P.dep && gate_reg_dims(P) && n_pos < INT32_MAX && gate_reg_has(nq);
     GateLookup gl{};
     if (reg && d->gcache) {
         if (d->glist_n[k] < n_pos) {
@@ -3268,13 +3216,11 @@ extern "C" int tm_dropin_forward(tm_dropin *d, int32_t k, int32_t sync, const tm
     }
     const unsigned lookup_blocks = gl.cnt ? (unsigned)((n_pos + 1023) / 1024) : 0u;
     // with the cache: the misses are computed by the lookup's own workgroups (std_cut_gate_kernel), no gate launch
-    const bool fused_gate = gl.cnt != nullptr && (nq == 11 || nq == 12 || nq == 13);
+    const bool fused_gate = gl.cnt != nullptr && std_cut_gate_has(nq);
     auto launch_std = [&](int32_t b_, const CutArg &c, double *cut_out, float *std_out, int32_t do_std) {
         const dim3 grid(1 + lookup_blocks);
-        if (!fused_gate) std_cut_kernel<<<grid, 1024, 0, side>>>(b_, W, c, ts3, cut_out, std_out, do_std, gl);
-        else if (nq == 11) std_cut_gate_kernel<11><<<grid, 1024, 0, side>>>(b_, W, c, ts3, cut_out, std_out, do_std, gl, P, e_feat);
-        else if (nq == 12) std_cut_gate_kernel<12><<<grid, 1024, 0, side>>>(b_, W, c, ts3, cut_out, std_out, do_std, gl, P, e_feat);
-        else std_cut_gate_kernel<13><<<grid, 1024, 0, side>>>(b_, W, c, ts3, cut_out, std_out, do_std, gl, P, e_feat);
+        if (!(fused_gate && launch_std_cut_gate(nq, grid, side, b_, W, c, ts3, cut_out, std_out, do_std, gl, P, e_feat)))
+            std_cut_kernel<<<grid, 1024, 0, side>>>(b_, W, c, ts3, cut_out, std_out, do_std, gl);
     };
     bool std_done = false;
     if (cut_host && B <= 256) {
@@ -3282,9 +3228,8 @@ extern "C" int tm_dropin_forward(tm_dropin *d, int32_t k, int32_t sync, const tm
         // buffer for the encoder (stream order keeps the buffer's previous readers ahead of it)
         CutArg c;
         memcpy(c.v, cut_host, sizeof(double) * (size_t)B);
-        float *stdv = reinterpret_cast<float *>(d->ws[k]) + n_walks * 3 * 2 * w->P.h;
         hipEvent_t pe = prof_begin(side);
-        launch_std(B, c, d->dcut[k], stdv, w->P.tg ? 1 : 0);
+        launch_std(B, c, d->dcut[k], enc_ws(w, n_walks, d->ws[k]).stdv, w->P.tg ? 1 : 0);
         TM_CHECK_LAUNCH();
         prof_end("std_kernel", side, pe);
         cut = d->dcut[k];
@@ -3324,34 +3269,22 @@ extern "C" int tm_dropin_forward(tm_dropin *d, int32_t k, int32_t sync, const tm
         launch_std(0, c, nullptr, nullptr, 0);
         TM_CHECK_LAUNCH();
     }
-    int rc = encoder_fwd_impl(w, n_feat, e_feat, etab, 1, B, W, 1, node6, eid3, ts3, cat, cut, cnt, d->ws[k], out_imp,
-                              side, !std_done);
-    if (rc != TM_OK) return rc;
+    EncFwd fwd{"tm_encoder_fwd", "tm_encoder_fwd_tab", w, n_feat, e_feat, etab, 1, B, W, 1, node6, eid3, ts3, cat, cut, cnt,
+               d->ws[k], out_imp, side};
+    fwd.do_std = !std_done;
+    if (int rc = encoder_forward(fwd)) return rc;
     if (out_gfac && !fused_gate) {
         const size_t lds = gate_lds(P);
         if (lds > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_dropin_forward: LDS budget exceeded");
         hipEvent_t pe = prof_begin(side);
         const unsigned rblocks = (unsigned)((n_pos + 63) / 64);
-        if (gl.cnt) {
-            // cached: the hits have their factor (the lookup), the misses (listed) run the register gate and fill
-            // the cache
-#define TM_GATE_LIST(Q)                                                                                            \
-    gate_reg_kernel<Q><<<dim3(rblocks), 256, 0, side>>>(P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, \
-                                                         ts3, gl.list, gl.cnt, d->gcache, d->gcache_n)
-            if (nq == 11) TM_GATE_LIST(11);
-            else if (nq == 12) TM_GATE_LIST(12);
-            else if (nq == 13) TM_GATE_LIST(13);
-            else TM_GATE_LIST(22);
-#undef TM_GATE_LIST
-        } else if (reg && nq == 11)
-            gate_reg_kernel<11><<<dim3(rblocks), 256, 0, side>>>(P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, ts3);
-        else if (reg && nq == 12)
-            gate_reg_kernel<12><<<dim3(rblocks), 256, 0, side>>>(P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, ts3);
-        else if (reg && nq == 13)
-            gate_reg_kernel<13><<<dim3(rblocks), 256, 0, side>>>(P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, ts3);
-        else if (reg)
-            gate_reg_kernel<22><<<dim3(rblocks), 256, 0, side>>>(P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, ts3);
-        else
+        // cached: the hits have their factor (the lookup), the misses (listed) run the register gate and fill the
+        // cache (gl.cnt set: reg holds, so the gate has its instance)
+        if (gl.cnt)
+            launch_gate_reg(nq, rblocks, side, P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3, ts3, gl.list,
+                            gl.cnt, d->gcache, d->gcache_n);
+        else if (!(reg && launch_gate_reg(nq, rblocks, side, P, (int32_t)n_pos, nullptr, e_feat, out_gfac, nullptr, eid3,
+                                          ts3)))
             gate_pos_kernel<<<dim3((unsigned)((n_pos + TILE_ROWS - 1) / TILE_ROWS)), 256, lds, side>>>(
                 P, n_pos, W, e_feat, eid3, ts3, nullptr, out_gfac);
         TM_CHECK_LAUNCH();
@@ -3413,8 +3346,7 @@ static int edge_importance_gf3(int32_t B, int32_t W, int32_t N, const float *gf0
         if (!a.gf[s] || !a.imp[s] || !a.eid3[s] || !a.s1n[s] || !a.s1e[s] || !a.s2n[s] || !a.s2e[s])
             return fail(TM_E_ARG, "tm_edge_importance_gf3: NULL pointer");
     if (!out_h1 || !out_h2) return fail(TM_E_ARG, "tm_edge_importance_gf3: NULL output");
-    int hbits = 6;
-    while ((1 << hbits) < 2 * 3 * W) ++hbits;
+    const int hbits = expl_hbits(W);
     if (hbits > 14) return fail(TM_E_UNSUPPORTED, "tm_edge_importance_gf3: too many walks per event");
     const size_t hlds = 2 * sizeof(int32_t) * (1u << hbits);
     hipEvent_t pe = prof_begin(S_(stream));
@@ -3434,8 +3366,7 @@ extern "C" int tm_edge_importance_gf(const float *gfac, int32_t n_groups, int32_
     if (rows == 0) return TM_OK;
     if (!gfac || !eid3 || !imp || !sub1_node || !sub1_eid || !sub2_node || !sub2_eid || !out_h1 || !out_h2)
         return fail(TM_E_ARG, "tm_edge_importance_gf: NULL pointer");
-    int hbits = 6;
-    while ((1 << hbits) < 2 * 3 * W) ++hbits;
+    const int hbits = expl_hbits(W);
     if (hbits > 14) return fail(TM_E_UNSUPPORTED, "tm_edge_importance_gf: too many walks per event");
     const size_t hlds = 2 * sizeof(int32_t) * (1u << hbits);
     hipEvent_t pe = prof_begin(S_(stream));

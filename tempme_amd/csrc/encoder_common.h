@@ -312,6 +312,13 @@ __device__ __forceinline__ void rgemm(const Lin &L, const floatx4 (&x)[NQ], floa
 bool launch_gcn_fwd_reg(const EncW &P, int node_zero, int64_t n_rows, const float *n_feat, const float *e_feat, const int32_t *node6,
                         const int32_t *eid3, const float *ts3, const float *cnt, float *F, hipStream_t s);
 
+// log2 of the explanation kernels' LDS hash size: at least 64 slots, and twice an event's 3 W walk positions
+inline int expl_hbits(int W) {
+    int hbits = 6;
+    while ((1 << hbits) < 2 * 3 * W) ++hbits;
+    return hbits;
+}
+
 // enhance.hip: the pooled encoder's tail, one workgroup per (group, event): out[e][0:h] = a2 (sum of the event's
 // n_part partial rows of `part`, in a fixed order) + a2.b * (sum of its W walk weights, in order), and with do_cat
 // out[e][h:h+12] = the event's category histogram
@@ -355,6 +362,35 @@ struct tm_weights {
 };
 
 void tm_weights_bump(tm_weights *w);   // encoder.hip: w->version = the next process-wide stamp
+
+// The encoder's workspace, written by the forwards and read back by tm_encoder_bwd / tm_encoder_pool_bwd:
+//   F [n_walks][3][2h] | the groups' std (n_walks + 64 floats) | 256 spare bytes
+// and for the pooled forwards, from the next multiple of 256 bytes on:
+//   the partial rows [n_walks][h] (the fused kernel uses n_slots * PM <= n_walks of them) | 256 spare bytes
+// The fused walk kernel leaves F unused and keeps the unit counter of its persistent launch in F's first word.
+struct EncWsLay {   // byte offsets from the workspace's start
+    int64_t stdv, bytes, part, pool_bytes;
+};
+inline EncWsLay enc_ws_lay(const tm_weights *w, int64_t n_walks) {
+    const int64_t h = w ? w->h : tmk::HID, f = sizeof(float);
+    EncWsLay l;
+    l.stdv = n_walks * 3 * 2 * h * f;
+    l.bytes = l.stdv + (n_walks + 64) * f + 256;
+    l.part = (l.bytes + 255) & ~(int64_t)255;
+    l.pool_bytes = l.part + n_walks * h * f + 256;
+    return l;
+}
+struct EncWs {
+    float *F, *stdv;
+    uint32_t *ticket;
+    float *part;   // only in a workspace of the pooled size
+};
+inline EncWs enc_ws(const tm_weights *w, int64_t n_walks, void *workspace) {
+    const EncWsLay l = enc_ws_lay(w, n_walks);
+    char *p = static_cast<char *>(workspace);
+    return {reinterpret_cast<float *>(p), reinterpret_cast<float *>(p + l.stdv), reinterpret_cast<uint32_t *>(p),
+            reinterpret_cast<float *>(p + l.part)};
+}
 
 // encoder_train.hip: transposed packs (tm_weights_create / _free) and the one-launch packing of every tensor
 int train_packs_create(tm_weights *w);

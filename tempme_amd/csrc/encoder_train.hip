@@ -1808,13 +1808,12 @@ extern "C" int tm_encoder_bwd(const tm_weights *w, const float *n_feat, const fl
     const size_t lh = sizeof(float) * head_bwd_lds_floats(P.h, P.hm, tr), lg = gcn_bwd_lds(P);
     if (P.h % 16 || !tr || lg > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_bwd: LDS budget exceeded");
     hipStream_t s = S_(stream);
-    const float *F = reinterpret_cast<const float *>(workspace);
-    const float *stdv = F + n_walks * 3 * 2 * P.h;
+    const EncWs ws = enc_ws(w, n_walks, const_cast<void *>(workspace));   // read only
     HeadBwdOut ho{io->imp, io->dlogit, io->M2, io->dM2, io->M1d, io->dM1, io->X, io->dY2, io->H1d, io->dH1, io->O,
                   io->dP,  io->dQ,     io->dF};
     hipEvent_t pe = prof_begin(s);
     head_bwd_kernel<16><<<dim3((unsigned)((n_walks + 15) / 16)), 256, lh, s>>>(
-        P, w->T, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, drop, drop_scale, d_imp, ho);
+        P, w->T, n_walks, (int64_t)B * W, W, ws.F, ts3, cut, cat, ws.stdv, drop, drop_scale, d_imp, ho);
     TM_CHECK_LAUNCH();
     prof_end("head_bwd_kernel", s, pe);
     return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
@@ -1842,13 +1841,12 @@ extern "C" int tm_encoder_pool_bwd(const tm_weights *w, const float *n_feat, con
     if (P.h % 16 || !head_bwd_tr(P) || gcn_bwd_lds(P) > 160 * 1024)
         return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_bwd: LDS budget exceeded");
     hipStream_t s = S_(stream);
-    const float *F = reinterpret_cast<const float *>(workspace);
-    const float *stdv = F + n_walks * 3 * 2 * P.h;
+    const EncWs ws = enc_ws(w, n_walks, const_cast<void *>(workspace));   // read only
     HeadBwdOut ho{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, io->dY2, io->H1d, io->dH1, io->O,
                   io->dP,  io->dQ,  io->dF};
     hipEvent_t pe = prof_begin(s);
     head_bwd_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, lh, s>>>(
-        P, w->T, n_walks, (int64_t)B * W, W, F, ts3, cut, cat, stdv, drop, drop_scale, nullptr, ho, wgt, d_emb, ld_demb);
+        P, w->T, n_walks, (int64_t)B * W, W, ws.F, ts3, cut, cat, ws.stdv, drop, drop_scale, nullptr, ho, wgt, d_emb, ld_demb);
     TM_CHECK_LAUNCH();
     prof_end("head_pool_bwd_kernel", s, pe);
     return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
@@ -2024,12 +2022,6 @@ extern "C" int tm_encoder_pool_wgrad(const tm_weights *w, int32_t n_groups, int3
                                     {grads[12], grads[13], 7, 1}, {grads[14], grads[15], 8, 1}};
     return run_wgrad(jobs, (int)(sizeof(jobs) / sizeof(jobs[0])), tgts, (int)(sizeof(tgts) / sizeof(tgts[0])),
                      S_(stream), "tm_encoder_pool_wgrad");
-}
-
-static int expl_hbits(int W) {
-    int hb = 6;
-    while ((1 << hb) < 2 * 3 * W) ++hb;
-    return hb;
 }
 
 static int explain_train_fwd(const tm_weights *w, const float *e_feat, int32_t n_groups, int32_t B, int32_t W,

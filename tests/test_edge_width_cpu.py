@@ -24,17 +24,18 @@ def r16(x):
 def dispatch(de, dn=EW.DN):
     """The instance an edge-feature width reaches, restated from tempme_amd/csrc:
 
-    * encoder.hip, encoder_fwd_impl: nqe = r16(kev) / 16, ntd = r16(dn) / 16; narrow = 11 <= nqe <= 14 and
-      de <= 16 * EQ_MAX; wide = nqe in (21, 22) and de > 16 * EQ_MAX and de % 4 == 0; the fused walk_kernel<nqe>
-      runs when ntd == 11, dn % 4 == 0 and (narrow or wide) (h = 64 with the category one-hot, as here), else
-      gcn_kernel + head_kernel.  launch_walk_pool takes the same instance table.
+    * encoder.hip, walk_pick (walk_nqe, walk_dims, walk_narrow, walk_wide_steps): nqe = r16(kev) / 16,
+      ntd = r16(dn) / 16; narrow = 11 <= nqe <= 14 and de <= 16 * EQ_MAX; wide = nqe in (21, 22) and
+      de > 16 * EQ_MAX and de % 4 == 0; the fused walk_kernel<nqe> runs when ntd == 11, dn % 4 == 0 and (narrow or
+      wide) (h = 64 with the category one-hot, as here), else gcn_kernel + head_kernel (launch_tiled).  The plain and
+      the pooled forward take the same instance table, launch_walk_pick.
     * encoder.hip, etab_q0: q0 = de / 16; a per-edge-id table for q0 == 2 with 11 <= nqe <= 14 and d1.nq == 13, or
       q0 == 10 with nqe in (21, 22) and d1.nq == 22 (d1.nq = r16(kdep) / 16, kdep = de + dn).
     * encoder.hip, load_ef (plain mode, narrow): the 32-wide step s is one float4 per half when de % 4 == 0 and
       32 s + 32 <= de, zero when 32 s >= de, else scalar loads clamped to the row; wide widths stream their row
       (ef_step).
     * encoder.hip, launch_edge_tables: with a table gate_reg_kernel<13, 3, nqe> (q0 == 2) or <22, 11, nqe>; without
-      one gate_reg_kernel<d1.nq> for d1.nq in (11, 12, 13, 22), else the LDS gate_table_kernel.
+      one gate_reg_kernel<d1.nq> for d1.nq in (11, 12, 13, 22) (launch_gate_reg), else the LDS gate_table_kernel.
     * encoder_train.hip, gcn_bwd_uses_reg / launch_gcn_fwd_reg: the register-resident event_gcn kernels at Q = nqe
       when r16(dn) == 176, dn % 4 == 0, de % 4 == 0 and 11 <= nqe <= 14, else the LDS-tiled ones.
     """

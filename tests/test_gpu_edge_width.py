@@ -9,7 +9,8 @@ count or time column moves it by at least 5 bounds.
 * table mode against the per-walk product, the edge table's values, and the explanation through the per-edge-id gate
   table (gate_reg_kernel<12>, <13>, <22>, <13, 3, 13 | 14>, <22, 11, 22> and the LDS gate_table_kernel);
 * the persistent form at de = 4 and 164, bit for bit against the split form;
-* the pooled forward (the POOL instances) at de = 4, 36 and 164.
+* the pooled forward (the POOL instances) at de = 4, 36 and 164, and its LDS-tiled path (gcn_kernel +
+  head_pool_kernel) at de = 50 and at hid_dim 32.
 """
 import numpy as np
 import pytest
@@ -176,14 +177,13 @@ def test_persistent_form_vs_oracle_and_split_form(dev, de):
 
 
 # ------------------------------------------------------------------ pooled forward (POOL instances)
-@pytest.mark.parametrize("de,table,zero_nodes", [(4, False, False), (4, False, True), (36, False, False),
-                                                 (36, True, False), (36, True, True), (164, False, False)])
-def test_pooled_forward_vs_fp64(dev, de, table, zero_nodes):
+def _pooled_vs_fp64(de, table, zero_nodes, hid_dim=64):
     """enhance_groups against tests/enhance_train_ref.groups in fp64: 10 times the restatement's own fp32-vs-fp64
-    distance at this shape (the convention of test_gpu_enhance_train.py), and twice the same bits."""
+    distance at this shape (the convention of test_gpu_enhance_train.py), and twice the same bits.  Returns the
+    profile's launch count per name of the first run."""
     import enhance_train_ref as TR
     from test_gpu_enhance_train import SHAPES, build
-    ex, d = build(shape=SHAPES["2x3x7"], de=de, zero_nodes=zero_nodes)
+    ex, d = build(shape=SHAPES["2x3x7"], de=de, zero_nodes=zero_nodes, hid_dim=hid_dim)
     ex.eval()
     sd, tg, ic = d["sd"], ex.use_temporal_guidance, ex.if_cat
     r64 = TR.groups({k: v.double() for k, v in sd.items()}, d, tg, ic)
@@ -195,12 +195,30 @@ def test_pooled_forward_vs_fp64(dev, de, table, zero_nodes):
         with torch.no_grad():
             return ex.enhance_groups(*d["args"], etab=etab).clone()
     a, count = profiled(fwd)
-    assert count("walk_pool_kernel") == 1 and count("pool_tail_kernel") == 1 and count("gcn_kernel") == 0
     assert ex._node_zero == zero_nodes
     b = fwd()
     dist = float((a.cpu().double() - r64).abs().max())
-    print("de %d table %d zero_nodes %d: pooled vs fp64 %.3g, tolerance %.3g, ratio %.3g"
-          % (de, table, zero_nodes, dist, tol, dist / tol))
+    print("de %d hid_dim %d table %d zero_nodes %d: pooled vs fp64 %.3g, tolerance %.3g, ratio %.3g"
+          % (de, hid_dim, table, zero_nodes, dist, tol, dist / tol))
     assert tuple(a.shape) == (d["G"], d["B"], ex.mlp_dim)
     assert dist <= tol
     assert torch.equal(a, b)
+    return count
+
+
+@pytest.mark.parametrize("de,table,zero_nodes", [(4, False, False), (4, False, True), (36, False, False),
+                                                 (36, True, False), (36, True, True), (164, False, False)])
+def test_pooled_forward_vs_fp64(dev, de, table, zero_nodes):
+    count = _pooled_vs_fp64(de, table, zero_nodes)
+    assert count("walk_pool_kernel") == 1 and count("pool_tail_kernel") == 1 and count("gcn_kernel") == 0
+
+
+@pytest.mark.parametrize("de,hid_dim,zero_nodes", [(50, 64, False), (50, 64, True), (32, 32, False)])
+def test_pooled_forward_tiled_path_vs_fp64(dev, de, hid_dim, zero_nodes):
+    """The same at dims the fused kernel refuses (15 K steps of 16 at de = 50; hid_dim 32): gcn_kernel, then
+    head_kernel's POOL instance, then the pool tail."""
+    count = _pooled_vs_fp64(de, False, zero_nodes, hid_dim)
+    assert count("gcn_kernel") == 1
+    assert count("head_pool_kernel") == 1
+    assert count("pool_tail_kernel") == 1
+    assert count("walk_pool_kernel") == 0

@@ -76,6 +76,30 @@ def test_flops_model_matches_survey():
     assert bench.sampling_bytes_per_event(30, 3) == 143_376
 
 
+def test_encoder_workspace_sizes():
+    """Python callers size their buffers from these three calls, and the backward reads F and the groups' std at the
+    offsets the forward wrote them: the byte counts are pinned.  No device is touched.  The size functions read only
+    tm_weights::h -- the struct begins with int device, de, dn, h (csrc/encoder_common.h) -- so a zeroed block with
+    that field set stands in for weights at hid_dim 32 (creating real ones needs a GPU); NULL means hid_dim 64."""
+    import ctypes as C
+    import tempme_amd
+    L = tempme_amd.lib()
+    want = {   # (h, n_walks): (tm_encoder_workspace_bytes, the two pooled sizes)
+        (32, 0): (512, 768), (32, 1): (1284, 1920), (32, 42): (32936, 38656), (32, 2 ** 20): (809501184, 943719168),
+        (64, 0): (512, 768), (64, 1): (2052, 2816), (64, 42): (65192, 76288), (64, 2 ** 20): (1614807552, 1883243264),
+    }
+    for (h, n), (plain, pool) in want.items():
+        # the layout itself: F [n][3][2h] | std, n + 64 floats | 256 spare bytes; pooled: that rounded up to 256,
+        # then the partials [n][h] and 256 spare bytes
+        assert plain == 4 * (6 * h * n + n + 64) + 256 and pool == (plain + 255) // 256 * 256 + 4 * h * n + 256
+        block = (C.c_int32 * 4096)()
+        block[3] = h
+        for w in ([C.addressof(block)] + ([None] if h == 64 else [])):
+            assert L.tm_encoder_workspace_bytes(w, n) == plain, (h, n)
+            assert L.tm_encoder_pool_workspace_bytes(w, n) == pool, (h, n)
+            assert L.tm_encoder_pool_train_workspace_bytes(w, n) == pool, (h, n)
+
+
 def test_dropin_extension_loads(monkeypatch):
     """The drop-in fast path's C++ host side (csrc/dropin_ext.cpp, built by build(), used whenever it is built)
     imports on the CPU and exposes its entry points (constructing one needs a HIP device)."""

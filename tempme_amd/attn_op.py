@@ -5,9 +5,10 @@ set of kernels (csrc/attn_kernels.h, csrc/attn_train.h); the flavour, ``spec["fl
 ``"tgat"``, selects the C entry points (the rounding of the time feature, and what each backward can return) and
 the label of the error messages.
 
-``spec`` is a dict of the descriptor's sizes and tensors: rows, n_ngh, n_head, d_key, d_node, d_edge, d_time,
-node_rows, edge_rows, head_major, seg_rows (optional), temperature, node_tab, node_idx, edge_tab, edge_idx (either
-may be None: a dense table), dt, time_w, time_b, mask_node, err.
+``spec`` is the dict of the descriptor's sizes and tensors that ``attn_layer.attn_spec`` builds (the one place that
+lists its keys).  The layer the two models build around this op -- folded projections, the multi-head tail, keep
+masks, the training opt-in, input preparation -- is attn_layer.py; ``as_dev`` here is the one host-or-device
+conversion every module of the package uses.
 """
 import numpy as np
 import torch
@@ -24,7 +25,8 @@ def _entry(spec, name):
     return getattr(L.lib(), f"tm_{spec['flavour']}_attn_{name}")
 
 
-def _as_dev(x, device, dtype):
+def as_dev(x, device, dtype):
+    """A tensor or host array on ``device`` in ``dtype`` (no copy where it already is)."""
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=dtype)
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x))).to(device=device, dtype=dtype)
@@ -152,4 +154,4 @@ class TrainAttnFn(torch.autograd.Function):
         return d_qf, d_node, d_tab, d_time[0], d_time[1], None, None, None
 
 
-__all__ = ["AttnFn", "TrainAttnFn", "describe"]
+__all__ = ["AttnFn", "TrainAttnFn", "describe", "as_dev"]

@@ -20,7 +20,8 @@ import torch
 from sklearn.metrics import average_precision_score, roc_auc_score
 
 from . import _lib as L
-from .attn_op import _as_dev
+from .attn_layer import stack_sides
+from .attn_op import as_dev
 
 
 def _masked_nodes(explanation, subgraphs, N, ratios, dev, hops=2):
@@ -29,7 +30,7 @@ def _masked_nodes(explanation, subgraphs, N, ratios, dev, hops=2):
     ne = N (graphmixer branch)."""
     ne = N + N * N if hops == 2 else N
     imp = torch.cat(list(explanation[:hops]), dim=1).to(dev, torch.float32).contiguous()
-    nodes = torch.cat([torch.cat([_as_dev(sg[0][h], dev, torch.int32) for h in range(hops)], dim=1)
+    nodes = torch.cat([torch.cat([as_dev(sg[0][h], dev, torch.int32) for h in range(hops)], dim=1)
                        for sg in subgraphs], dim=0).contiguous()
     rows = nodes.shape[0]
     if imp.shape != (rows, ne):
@@ -42,28 +43,33 @@ def _masked_nodes(explanation, subgraphs, N, ratios, dev, hops=2):
     return out
 
 
-def masked_contrast(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src, subgraph_tgt,
-                    subgraph_bgd, n_degree, ratios):
-    """(pos [G, B], neg [G, B]) logits of contrast on the masked subgraph of every ratio."""
-    dev = base_model._dev()
-    B, N, G = len(src_l_cut), n_degree, len(ratios)
-    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
-    masked = _masked_nodes(explanation, sgs, N, ratios, dev)                          # [G, 3B, ne]
-    roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_l_cut, dst_l_cut, dst_l_fake)])
-    n1 = masked[:, :, :N].reshape(G * 3 * B, N)
-    n2 = masked[:, :, N:].reshape(G * 3 * B, N * N)
-
-    def rep(i, h, dtype):
-        x = torch.cat([_as_dev(sg[i][h], dev, dtype) for sg in sgs], dim=0)
-        return x.repeat(G, 1)
-    emb = base_model.node_embeddings([roots.repeat(G), n1, n2], [rep(1, 0, torch.int32), rep(1, 1, torch.int32)],
-                                     [rep(2, 0, torch.float64), rep(2, 1, torch.float64)], ts_l_cut, n_segments=G)
+def _pair_scores(base_model, emb, G, B):
+    """(pos [G, B], neg [G, B]) from the [G 3B, d] embeddings of every ratio's src, tgt, bgd sides."""
     emb = emb.view(G, 3, B, -1)
     s, d, n = emb[:, 0], emb[:, 1], emb[:, 2]
     x1 = torch.cat([s, s], dim=1).reshape(G * 2 * B, -1)
     x2 = torch.cat([d, n], dim=1).reshape(G * 2 * B, -1)
     score = base_model.affinity(x1, x2).view(G, 2 * B)
     return score[:, :B], score[:, B:]
+
+
+def masked_contrast(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src, subgraph_tgt,
+                    subgraph_bgd, n_degree, ratios, side_segments=False):
+    """(pos [G, B], neg [G, B]) logits of contrast on the masked subgraph of every ratio: [hop-1 | hop-2] records
+    masked, then contrast without weights, all ratios in one batch.  ``explanation``: (hop-1 [3B, N], hop-2
+    [3B, N^2]).  ``side_segments`` (tgat): every (ratio, side) is one forward_msg call of B rows, a segment of its
+    own; else (tgn) a ratio's three sides are one segment."""
+    dev = base_model._dev()
+    B, N, G = len(src_l_cut), n_degree, len(ratios)
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    masked = _masked_nodes(explanation, sgs, N, ratios, dev)                          # [G, 3B, ne]
+    roots, _, eids, times = stack_sides(dev, (src_l_cut, dst_l_cut, dst_l_fake), sgs, nodes=False)
+    n1 = masked[:, :, :N].reshape(G * 3 * B, N)
+    n2 = masked[:, :, N:].reshape(G * 3 * B, N * N)
+    emb = base_model.node_embeddings([roots.repeat(G), n1, n2], [x.repeat(G, 1) for x in eids],
+                                     [x.repeat(G, 1) for x in times], ts_l_cut,
+                                     n_segments=3 * G if side_segments else G)
+    return _pair_scores(base_model, emb, G, B)
 
 
 def masked_contrast_graphmixer(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
@@ -73,46 +79,19 @@ def masked_contrast_graphmixer(base_model, explanation, src_l_cut, dst_l_cut, ds
     B, N, G = len(src_l_cut), n_degree, len(ratios)
     sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
     masked = _masked_nodes(explanation, sgs, N, ratios, dev, hops=1).reshape(G * 3 * B, N)
-    roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_l_cut, dst_l_cut, dst_l_fake)])
-    cut = _as_dev(ts_l_cut, dev, torch.float64).reshape(-1).repeat(3 * G)
-
-    def rep(i, dtype):
-        return torch.cat([_as_dev(sg[i][0], dev, dtype) for sg in sgs], dim=0).repeat(G, 1)
-    emb = base_model.node_embeddings(roots.repeat(G), cut, masked, rep(1, torch.long), rep(2, torch.float64))
-    emb = emb.view(G, 3, B, -1)
-    s, d, n = emb[:, 0], emb[:, 1], emb[:, 2]
-    x1 = torch.cat([s, s], dim=1).reshape(G * 2 * B, -1)
-    x2 = torch.cat([d, n], dim=1).reshape(G * 2 * B, -1)
-    score = base_model.affinity(x1, x2).view(G, 2 * B)
-    return score[:, :B], score[:, B:]
+    roots, _, (eid,), (t,) = stack_sides(dev, (src_l_cut, dst_l_cut, dst_l_fake), sgs, nodes=False, hops=1,
+                                         idx_dtype=torch.long)
+    cut = as_dev(ts_l_cut, dev, torch.float64).reshape(-1).repeat(3 * G)
+    emb = base_model.node_embeddings(roots.repeat(G), cut, masked, eid.repeat(G, 1), t.repeat(G, 1))
+    return _pair_scores(base_model, emb, G, B)
 
 
-def masked_contrast_tgat(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
-                         subgraph_tgt, subgraph_bgd, n_degree, ratios):
-    """tgat branch (temp_exp_main.py:216-250): the explanation is the per-side 6-list
-    [src0, src1, tgt0, tgt1, bgd0, bgd1]; [hop-1 | hop-2] records masked, then contrast without weights.
-    All ratios in one batch: every (ratio, side) is one forward_msg call of B rows, a segment of its own."""
+def masked_contrast_tgat(base_model, explanation, *batch):
+    """tgat branch (temp_exp_main.py:216-250): masked_contrast for the per-side 6-list explanation
+    [src0, src1, tgt0, tgt1, bgd0, bgd1], every (ratio, side) a segment."""
     dev = base_model._dev()
-    B, N, G = len(src_l_cut), n_degree, len(ratios)
-    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
     stacked = [torch.cat([explanation[2 * s + h].to(dev) for s in range(3)], dim=0) for h in (0, 1)]
-    masked = _masked_nodes(stacked, sgs, N, ratios, dev)                              # [G, 3B, ne]
-    roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_l_cut, dst_l_cut, dst_l_fake)])
-    n1 = masked[:, :, :N].reshape(G * 3 * B, N)
-    n2 = masked[:, :, N:].reshape(G * 3 * B, N * N)
-
-    def rep(i, h, dtype):
-        x = torch.cat([_as_dev(sg[i][h], dev, dtype) for sg in sgs], dim=0)
-        return x.repeat(G, 1)
-    emb = base_model.node_embeddings([roots.repeat(G), n1, n2], [rep(1, 0, torch.int32), rep(1, 1, torch.int32)],
-                                     [rep(2, 0, torch.float64), rep(2, 1, torch.float64)], ts_l_cut,
-                                     n_segments=3 * G)
-    emb = emb.view(G, 3, B, -1)
-    s, d, n = emb[:, 0], emb[:, 1], emb[:, 2]
-    x1 = torch.cat([s, s], dim=1).reshape(G * 2 * B, -1)
-    x2 = torch.cat([d, n], dim=1).reshape(G * 2 * B, -1)
-    score = base_model.affinity(x1, x2).view(G, 2 * B)
-    return score[:, :B], score[:, B:]
+    return masked_contrast(base_model, stacked, *batch, side_segments=True)
 
 
 def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, e_l_cut,

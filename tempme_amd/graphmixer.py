@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .attn_op import _as_dev
+from .attn_op import as_dev
 from .tgn import MergeLayer
 
 
@@ -455,29 +455,29 @@ class GraphMixer(nn.Module):
         dev = self._dev()
         N0 = np.shape(nid)[-1]
         if self._train_hip_ok(explain_weight, edge_attr, N0):
-            return self._embed_train_hip(dev, _as_dev(node_ids, dev, torch.long).reshape(-1),
-                                         _as_dev(cut_time, dev, torch.float64).reshape(-1),
-                                         _as_dev(nid, dev, torch.long), _as_dev(eid, dev, torch.long),
-                                         _as_dev(times, dev, torch.float64))
+            return self._embed_train_hip(dev, as_dev(node_ids, dev, torch.long).reshape(-1),
+                                         as_dev(cut_time, dev, torch.float64).reshape(-1),
+                                         as_dev(nid, dev, torch.long), as_dev(eid, dev, torch.long),
+                                         as_dev(times, dev, torch.float64))
         mode = self._hip_mode(explain_weight, N0)
         if mode is not None:
-            return self._embed_hip(dev, _as_dev(node_ids, dev, torch.long).reshape(-1),
-                                   _as_dev(cut_time, dev, torch.float64).reshape(-1), _as_dev(nid, dev, torch.long),
-                                   _as_dev(eid, dev, torch.long), _as_dev(times, dev, torch.float64), explain_weight,
-                                   None if edge_attr is None else _as_dev(edge_attr, dev, torch.float32), mode)
+            return self._embed_hip(dev, as_dev(node_ids, dev, torch.long).reshape(-1),
+                                   as_dev(cut_time, dev, torch.float64).reshape(-1), as_dev(nid, dev, torch.long),
+                                   as_dev(eid, dev, torch.long), as_dev(times, dev, torch.float64), explain_weight,
+                                   None if edge_attr is None else as_dev(edge_attr, dev, torch.float32), mode)
         ntab, etab = self._tables(dev)
-        node_ids = _as_dev(node_ids, dev, torch.long).reshape(-1)
-        nid = _as_dev(nid, dev, torch.long)
+        node_ids = as_dev(node_ids, dev, torch.long).reshape(-1)
+        nid = as_dev(nid, dev, torch.long)
         valid = nid != 0
-        t = _as_dev(times, dev, torch.float64)
-        cut = _as_dev(cut_time, dev, torch.float64).reshape(-1, 1)
+        t = as_dev(times, dev, torch.float64)
+        cut = as_dev(cut_time, dev, torch.float64).reshape(-1, 1)
         ew = None
         if explain_weight is not None:
             ew = explain_weight.to(dev, torch.float32) * valid.to(torch.float32)
         if edge_attr is None:
-            ef = etab[_as_dev(eid, dev, torch.long)] * valid.unsqueeze(-1)
+            ef = etab[as_dev(eid, dev, torch.long)] * valid.unsqueeze(-1)
         else:
-            ef = _as_dev(edge_attr, dev, torch.float32)
+            ef = as_dev(edge_attr, dev, torch.float32)
         tf = self.time_encoder.encode((cut - t).float()) * valid.unsqueeze(-1)
         x = F.linear(torch.cat([ef, tf], dim=-1), self.projection_layer.weight.to(dev),
                      self.projection_layer.bias.to(dev))
@@ -501,11 +501,11 @@ class GraphMixer(nn.Module):
         B = len(src_idx)
         dev = self._dev()
         sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
-        roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_idx, tgt_idx, bgd_idx)])
-        cut = _as_dev(cut_time, dev, torch.float64).reshape(-1).repeat(3)
-        nid = torch.cat([_as_dev(sg[0][0], dev, torch.long) for sg in sgs])
-        eid = torch.cat([_as_dev(sg[1][0], dev, torch.long) for sg in sgs])
-        t = torch.cat([_as_dev(sg[2][0], dev, torch.float64) for sg in sgs])
+        roots = torch.cat([as_dev(x, dev, torch.long).reshape(-1) for x in (src_idx, tgt_idx, bgd_idx)])
+        cut = as_dev(cut_time, dev, torch.float64).reshape(-1).repeat(3)
+        nid = torch.cat([as_dev(sg[0][0], dev, torch.long) for sg in sgs])
+        eid = torch.cat([as_dev(sg[1][0], dev, torch.long) for sg in sgs])
+        t = torch.cat([as_dev(sg[2][0], dev, torch.float64) for sg in sgs])
         ew = explain_weights[0] if explain_weights is not None else None
         emb = self.node_embeddings(roots, cut, nid, eid, t, ew, edge_attr)
         return emb[:B], emb[B:2 * B], emb[2 * B:]
@@ -526,7 +526,7 @@ class GraphMixer(nn.Module):
         """graphmixer.py:196-201."""
         dev = self._dev()
         _, etab = self._tables(dev)
-        return torch.cat([etab[_as_dev(sg[1][0], dev, torch.long)] for sg in (subgraph_src, subgraph_tgt,
+        return torch.cat([etab[as_dev(sg[1][0], dev, torch.long)] for sg in (subgraph_src, subgraph_tgt,
                                                                               subgraph_bgd)], dim=0)
 
     def set_neighbor_sampler(self, neighbor_sampler):

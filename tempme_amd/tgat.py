@@ -37,6 +37,11 @@ inside the kernels, fc's dropout in the torch tail, P = W_k^T W_q and G = fc W_v
 parameters under autograd (so d qf and d z reach w_qs, w_ks, w_vs and fc), the query-side time features as
 differentiable torch ops and the key-side time gradient from the kernel's d_time.  ``loss.backward()`` then fills
 .grad on all 36 trainable parameters.
+
+The layer around the op is attn_layer.py's, shared with tgn.py (``fold``: this module multiplies by contiguous
+P^T / G^T -- the packs transpose the fp64 pair, the training step asks for the transposed products).  TGAT's own: the
+two-branch merger with its optional fused ``merge_fwd``, the time features ``cos(dt * freq + phase)`` (two roundings),
+``keep_mask_shapes`` and the query cache of ``prepare_contrast``.
 """
 import numpy as np
 import torch
@@ -44,8 +49,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .attn_op import AttnFn, TrainAttnFn, _as_dev
-from .tgn import _cat_rows
+from . import attn_layer as AL
+from .attn_op import AttnFn, TrainAttnFn
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -150,8 +155,7 @@ def merge_fwd(z, query, lw, feat):
 
 def merge_torch(z, query, lw, feat):
     """The same tail as torch ops (differentiable; the reference's order of operations)."""
-    out = torch.addmm(lw["fcb"], z, lw["Gt"])
-    h = F.layer_norm(out + query, (query.shape[1],), lw["lnw"], lw["lnb"], 1e-5)
+    h = AL.mha_tail(z, query, lw["Gt"], lw["fcb"], lw["lnw"], lw["lnb"])
     x1 = torch.addmm(lw["b21"], F.relu(torch.addmm(lw["b11"], h, lw["w11t"])), lw["w21t"])
     x2 = torch.addmm(lw["b22"], F.relu(torch.addmm(lw["b12"], query[:, :feat], lw["w12t"])), lw["w22t"])
     return x2 + x1
@@ -160,16 +164,10 @@ def merge_torch(z, query, lw, feat):
 def pack_attn_model(am, dev):
     """Folded, device-resident weights of one AttnModel: P = W_k^T W_q and G = fc W_v per head, folded in
     fp64 and stored in fp32; the tail's matrices transposed ([in][out]) as tm_tgat_merge_fwd reads them."""
-    f32, f64 = torch.float32, torch.float64
+    f32 = torch.float32
     mh, mg = am.multi_head_target, am.merger
-    H, dh = mh.n_head, mh.d_k
-    dm = mh.w_qs.weight.shape[1]
-    wq = mh.w_qs.weight.detach().to(dev, f64).view(H, dh, dm)
-    wk = mh.w_ks.weight.detach().to(dev, f64).view(H, dh, dm)
-    wv = mh.w_vs.weight.detach().to(dev, f64).view(H, dh, dm)
-    fc = mh.fc.weight.detach().to(dev, f64).view(dm, H, dh)
-    P = torch.einsum("hoi,hoq->hiq", wk, wq).reshape(H * dm, dm)          # qf = P query  [H*dm]
-    G = torch.einsum("qho,hoi->qhi", fc, wv).reshape(dm, H * dm)          # fc(...) = G z
+    P, G = AL.fold(mh, torch.float64, dev)           # qf = P query [H*dm], fc(...) = G z
+    H, dm = mh.n_head, P.shape[1]
 
     def t(lin):
         return lin.weight.detach().to(dev, f32).t().contiguous()
@@ -185,8 +183,14 @@ def pack_attn_model(am, dev):
 
 
 # ------------------------------------------------------------------ the model
-class TGAT(nn.Module):
-    """TGAT/TGAT.py:389-423 constructor (same arguments, parameter names and initialisation order)."""
+class TGAT(AL.HipTraining, nn.Module):
+    """TGAT/TGAT.py:389-423 constructor (same arguments, parameter names and initialisation order).
+
+    ``train_on_hip()`` (attn_layer.HipTraining) opts in to the HIP training step: ``train()`` calls of contrast /
+    get_node_emb with gradients enabled and ``if_explain`` false run tm_tgat_attn_train_fwd /
+    tm_tgat_attn_train_bwd, and ``loss.backward()`` fills ``.grad`` on all 36 trainable parameters."""
+    _label = "TGAT"
+    _param_error = "TGAT.train_on_hip: parameters must be contiguous fp32 on the HIP device"
 
     def __init__(self, n_feat, e_feat, num_neighbors, attn_mode="prod", use_time="time", attn_agg_method="attn",
                  num_layers=3, n_head=4, drop_out=0.1, verbosity=1):
@@ -271,11 +275,9 @@ class TGAT(nn.Module):
         lw = pk["models"][mi]
         H, dk, fd = lw["H"], lw["dk"], self.feat_dim
         query, qf = q if q is not None else self._query(lw, src, src_t, R)
-        spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=fd, d_edge=self.e_feat_dim, d_time=self.time_dim,
-                    node_rows=pk["tab"].shape[0], edge_rows=pk["etab"].shape[0], head_major=self.head_major_rows,
-                    temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"],
-                    edge_idx=edge_idx, dt=dt, time_w=pk["freq"], time_b=pk["phase"], mask_node=mask_node,
-                    err=pk["err"], seg_rows=seg, flavour="tgat")
+        spec = AL.attn_spec("tgat", R, N, H, dk, fd, self.time_dim, lw["temperature"], self.head_major_rows, seg,
+                            node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"], edge_idx=edge_idx, dt=dt,
+                            time_w=pk["freq"], time_b=pk["phase"], mask_node=mask_node, err=pk["err"])
         z = AttnFn.apply(qf, ngh_dense, ew, spec)
         if self.fused_tail and not (torch.is_grad_enabled() and (z.requires_grad or query.requires_grad)):
             return merge_fwd(z, query, lw, fd)
@@ -300,29 +302,7 @@ class TGAT(nn.Module):
     def _prep_inputs(self, nodes, eids, times, cut_time, n_segments=1):
         """What node_embeddings derives from its inputs before any weight is read: the node, edge-id and time
         tensors on the device in the kernels' dtypes and the two time offsets (a dict)."""
-        dev = self._dev()
-        i32, f64 = torch.int32, torch.float64
-        n0 = _as_dev(nodes[0], dev, torch.long).reshape(-1)
-        R = n0.shape[0]
-        n1 = _as_dev(nodes[1], dev, i32).reshape(R, -1).contiguous()
-        N = n1.shape[1]
-        n2 = _as_dev(nodes[2], dev, i32).reshape(R * N, N).contiguous()
-        e1 = _as_dev(eids[0], dev, i32).reshape(R, N).contiguous()
-        e2 = _as_dev(eids[1], dev, i32).reshape(R * N, N).contiguous()
-        cut = _as_dev(cut_time, dev, f64).reshape(-1)
-        if R % n_segments:
-            raise AssertionError("rows must split evenly into n_segments")
-        seg = R // n_segments
-        if cut.shape[0] == seg and seg != R:
-            cut = cut.repeat(n_segments)
-        if cut.shape[0] != R:
-            raise AssertionError("cut_time must give one time per row (or per row of one segment)")
-        t1 = _as_dev(times[0], dev, f64).reshape(R, N)
-        t2 = _as_dev(times[1], dev, f64).reshape(R, N, N)
-        dt1 = (cut.view(R, 1) - t1).float().contiguous()                   # retrieve_time_features :653-666
-        dt2 = (t1.view(R, N, 1) - t2).float().contiguous()
-        return dict(dev=dev, R=R, N=N, seg=seg, n_segments=n_segments, n0=n0, n1=n1, n2=n2, e1=e1, e2=e2, dt1=dt1,
-                    dt2=dt2)
+        return AL.prep_inputs(self._dev(), nodes, eids, times, cut_time, n_segments)
 
     def _embed(self, x, explain_weights=None):
         """The three passes of node_embeddings on ``_prep_inputs``' dict ``x``."""
@@ -349,7 +329,7 @@ class TGAT(nn.Module):
             t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)         # two roundings (mul, then add)
             lw = pk["models"][0]
             q0 = self._query(lw, tab[n0], t_root, R)
-            q1 = self._query(lw, tab[n1.reshape(-1).long()], t_hop1, R * N)
+            q1 = self._query(lw, tab[n1.long()], t_hop1, R * N)
             if cache is not None:
                 cache["pack"], cache["q"] = pk, (q0, q1)
         h0 = self._attn_pass(pk, 0, None, None, R, N, n1, None, e1, dt1, n1, ew1, seg, q0)
@@ -357,22 +337,6 @@ class TGAT(nn.Module):
         return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg)
 
     # -------------------------------------------------------------- HIP training path (tm_tgat_attn_train_*)
-    def train_on_hip(self, flag=True):
-        """Opt in to (or out of) the HIP training step: with the flag set, ``model.train()`` calls of contrast /
-        get_node_emb with gradients enabled and ``if_explain`` false run tm_tgat_attn_train_fwd /
-        tm_tgat_attn_train_bwd with the reference's two dropouts, and ``loss.backward()`` fills ``.grad`` on all
-        36 trainable parameters (learn_base.py).  Default off: every other call keeps its path."""
-        self._train_on_hip = bool(flag)
-        self._train_checked = None
-        return self
-
-    def _apply(self, fn, *args, **kwargs):
-        self._train_checked = None          # .to() / .float() / ...: the parameters are looked at again
-        return super()._apply(fn, *args, **kwargs)
-
-    def _train_hip_ok(self):
-        return bool(getattr(self, "_train_on_hip", False)) and self.training and torch.is_grad_enabled()
-
     def keep_mask_shapes(self, R, N):
         """Shapes of one step's six keep masks for R stacked rows: the attention masks of the three passes
         (flat, the byte of (row, head, neighbour) at (row H + head) N + neighbour: the reference's dropped tensor
@@ -383,103 +347,56 @@ class TGAT(nn.Module):
     def draw_keep_masks(self, R, N, generator=None):
         """One step's keep masks (uint8, 1 = kept with probability 1 - drop_out) for R stacked rows, drawn on
         the device in one allocation: [attn pass 1, attn pass 2, attn pass 3, fc pass 1, fc pass 2, fc pass 3]."""
-        shapes = self.keep_mask_shapes(R, N)
-        sizes = [int(np.prod(sh)) for sh in shapes]
-        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=self._dev()).bernoulli_(
-            1.0 - float(self.dropout_p), generator=generator)
-        return [x.view(sh) for x, sh in zip(flat.split(sizes), shapes)]
-
-    def _fold_live(self, am):
-        """Pt [dm, H dm] and Gt [H dm, dm] of pack_attn_model from the live parameters, in fp32 under autograd."""
-        mh = am.multi_head_target
-        H, dh = mh.n_head, mh.d_k
-        dm = mh.w_qs.weight.shape[1]
-        wq, wk, wv = (w.weight.view(H, dh, dm) for w in (mh.w_qs, mh.w_ks, mh.w_vs))
-        Pt = torch.einsum("hoi,hoq->qhi", wk, wq).reshape(dm, H * dm)
-        Gt = torch.einsum("qho,hoi->hiq", mh.fc.weight.view(dm, H, dh), wv).reshape(H * dm, dm)
-        return Pt, Gt
+        return AL.draw_keep_masks(self.keep_mask_shapes(R, N), self.dropout_p, self._dev(), generator)
 
     def _train_pass(self, am, folded, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, seg, akeep,
                     fkeep, scale):
         """_attn_pass on the live parameters with both dropouts -> [R, feat]."""
-        mh, mg = am.multi_head_target, am.merger
+        mh = am.multi_head_target
         Pt, Gt = folded
-        fd, dm = self.feat_dim, self.model_dim
         te = self.time_encoder
         query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)
         qf = (query @ Pt).contiguous()
-        spec = dict(rows=R, n_ngh=N, n_head=mh.n_head, d_key=dm, d_node=fd, d_edge=self.e_feat_dim,
-                    d_time=self.time_dim, node_rows=self.n_feat_th.shape[0], edge_rows=self.e_feat_th.shape[0],
-                    head_major=self.head_major_rows, temperature=mh.temperature, node_tab=self.n_feat_th,
-                    node_idx=node_idx, edge_tab=self.e_feat_th, edge_idx=edge_idx, dt=dt, time_w=te.basis_freq.detach(),
-                    time_b=te.phase.detach(), mask_node=mask_node, err=self._train_err, seg_rows=seg, flavour="tgat")
+        spec = AL.attn_spec("tgat", R, N, mh.n_head, self.model_dim, self.feat_dim, self.time_dim, mh.temperature,
+                            self.head_major_rows, seg, node_tab=self.n_feat_th, node_idx=node_idx,
+                            edge_tab=self.e_feat_th, edge_idx=edge_idx, dt=dt, mask_node=mask_node, err=self._train_err)
         z = TrainAttnFn.apply(qf, ngh_dense, None, te.basis_freq, te.phase, spec, akeep, scale)
-        out = torch.addmm(mh.fc.bias, z, Gt)
-        if fkeep is not None:
-            out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (TGAT.py:134)
-        h = F.layer_norm(out + query, (dm,), mh.layer_norm.weight, mh.layer_norm.bias, 1e-5)
-        return mg(h, query[:, :fd])
+        # fc's dropout: TGAT.py:134
+        h = AL.mha_tail(z, query, Gt, mh.fc.bias, mh.layer_norm.weight, mh.layer_norm.bias, fkeep, scale)
+        return am.merger(h, query[:, :self.feat_dim])
 
     def _embed_train(self, dev, R, N, seg, n0, n1, n2, e1, e2, dt1, dt2):
         """The three passes of node_embeddings on the HIP training path (no explanation weights)."""
         te = self.time_encoder
-        if getattr(self, "_train_checked", None) != dev:       # once per train_on_hip() / .to(), not per step
-            for p in self.parameters():
-                if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("TGAT.train_on_hip: parameters must be contiguous fp32 on the HIP device")
-            self._train_checked = dev
-        if getattr(self, "_train_err", None) is None or self._train_err.device != dev:
-            self._train_err = torch.zeros(1, dtype=torch.int32, device=dev)
-        p = float(self.dropout_p)
-        keep = getattr(self, "tgat_keep_masks", None)
-        if keep is None and p > 0.0:
-            keep = self.draw_keep_masks(R, N)
-        if keep is not None:
-            shapes = self.keep_mask_shapes(R, N)
-            if len(keep) != 6 or any(k.dtype != torch.uint8 or k.device != dev or k.numel() != int(np.prod(sh))
-                                     for k, sh in zip(keep, shapes)):
-                raise ValueError("TGAT.tgat_keep_masks: expected draw_keep_masks(R, N)'s six uint8 masks on the device")
-            keep = [k.contiguous().view(sh) for k, sh in zip(keep, shapes)]
-        else:
-            keep = [None] * 6
-        scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+        self._live_state(dev)
+        keep, scale = AL.step_keep_masks(
+            getattr(self, "tgat_keep_masks", None), self.keep_mask_shapes(R, N), float(self.dropout_p), dev,
+            "TGAT.tgat_keep_masks: expected draw_keep_masks(R, N)'s six uint8 masks on the device")
         tab = self.n_feat_th
         freq, phase = te.basis_freq, te.phase
         t_root = torch.cos(torch.zeros_like(freq) * freq + phase).expand(R, -1)          # TimeEncode(0)
         t_hop1 = torch.cos(dt1.reshape(-1, 1) * freq + phase)                           # two roundings (mul, then add)
         am0, am1 = self.attn_model_list
-        f0, f1 = self._fold_live(am0), self._fold_live(am1)
+        # contiguous Pt [dm, H dm] / Gt [H dm, dm], as the pack's: folded in fp32 from the live parameters
+        f0, f1 = (AL.fold(am.multi_head_target, transposed=True) for am in (am0, am1))
         h0 = self._train_pass(am0, f0, tab[n0], t_root, R, N, n1, None, e1, dt1, n1, seg, keep[0], keep[3], scale)
-        h1 = self._train_pass(am0, f0, tab[n1.reshape(-1).long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, seg * N,
+        h1 = self._train_pass(am0, f0, tab[n1.long()], t_hop1, R * N, N, n2, None, e2, dt2, n2, seg * N,
                               keep[1], keep[4], scale)
         out = self._train_pass(am1, f1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, seg, keep[2], keep[5],
                                scale)
         self._tgat_train_key = (R, N, keep[0] is not None)   # marker: the HIP training path ran
         return out
 
-    def check_errors(self):
-        """Raise if a kernel saw an out-of-range node or edge index (synchronises)."""
-        pk = self._pack_cache
-        for err in ((pk or {}).get("err"), getattr(self, "_train_err", None)):
-            if err is not None and int(err.item()) != 0:
-                err.zero_()
-                raise IndexError("TGAT: node or edge index out of range of the feature tables")
-
     def _sides(self, roots, subgraphs, weights, cut_time):
         """Stack the sides of a contrast into one node_embeddings call -> list of [B, feat]."""
         self._check_mode(weights)
         dev = self._dev()
         S = len(roots)
-        n0 = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in roots])
-
-        def cat(i, h, dtype):
-            return torch.cat([_as_dev(sg[i][h], dev, dtype) for sg in subgraphs])
+        n0, nodes, eids, times = AL.stack_sides(dev, roots, subgraphs)
         ew = None
         if weights is not None:
             ew = [torch.cat([w[h].to(dev, torch.float32) for w in weights]) for h in (0, 1)]
-        emb = self.node_embeddings([n0, cat(0, 0, torch.int32), cat(0, 1, torch.int32)],
-                                   [cat(1, 0, torch.int32), cat(1, 1, torch.int32)],
-                                   [cat(2, 0, torch.float64), cat(2, 1, torch.float64)], cut_time, ew, n_segments=S)
+        emb = self.node_embeddings([n0] + nodes, eids, times, cut_time, ew, n_segments=S)
         B = emb.shape[0] // S
         return list(emb.split(B)) if B > 0 else [emb[:0]] * S
 
@@ -489,28 +406,15 @@ class TGAT(nn.Module):
         (without and with explanation weights, temp_exp_main.py:597, :611) share them through
         ``contrast(..., prepared=...)``.  The dict also keeps the queries of the first two passes once a contrast
         has folded them (they depend on the batch and the frozen weights only)."""
-        dev = self._dev()
-        sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
-        roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_idx_l, tgt_idx_l, bgd_idx_l)])
-
-        def cat(i, h, dtype):
-            xs = [sg[i][h] for sg in sgs]
-            if all(isinstance(x, torch.Tensor) and x.device == dev for x in xs):
-                # the three sides of a gathered pack are consecutive rows of one tensor: one view, and one
-                # dtype conversion instead of three (elementwise, so the same values as convert-then-cat)
-                return _as_dev(_cat_rows(xs), dev, dtype)
-            return torch.cat([_as_dev(x, dev, dtype) for x in xs])
-        x = self._prep_inputs([roots, cat(0, 0, torch.int32), cat(0, 1, torch.int32)],
-                              [cat(1, 0, torch.int32), cat(1, 1, torch.int32)],
-                              [cat(2, 0, torch.float64), cat(2, 1, torch.float64)], cut_time_l, n_segments=3)
+        n0, nodes, eids, times = AL.stack_sides(self._dev(), (src_idx_l, tgt_idx_l, bgd_idx_l),
+                                                (subgraph_src, subgraph_tgt, subgraph_bgd))
+        x = self._prep_inputs([n0] + nodes, eids, times, cut_time_l, n_segments=3)
         x["cache"] = {}
         return x
 
     # -------------------------------------------------------------- reference API
     def affinity(self, x1, x2):
-        pk = self._pack()
-        h = F.relu(F.linear(torch.cat([x1, x2], dim=1), pk["a1w"], pk["a1b"]))
-        return F.linear(h, pk["a2w"], pk["a2b"])
+        return AL.affinity(self._pack(), x1, x2)
 
     def _score3(self, emb, live):
         """(pos, neg) scores from the [3B, feat] embeddings of the segments src, tgt, bgd: [tgt; bgd] is emb's

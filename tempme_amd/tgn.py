@@ -35,6 +35,11 @@ and the GRU cell (through the updated memory rows the keys and queries gather: `
 ``tm_tgn_rows_reduce``, no atomics), the two attention layers and ``affinity_score``.  ``messages_to_dict()`` /
 ``messages_from_dict()`` move the pending messages between the device store and ``memory.messages``, which the
 frozen path reads (it calls the former itself when the store is newer).
+
+The layer around the op is attn_layer.py's, shared with tgat.py (``fold``: this module multiplies by the ``.t()``
+views of the row-major P, G; ``prep_inputs`` with ``sides=3`` and ``seg`` 0 for a single segment).  TGN's own: the
+one-MergeLayer merger over [h | src], ``cos(time bias)`` as the query's time feature, ``keep_mask_shapes``, the
+gathered node table with its gradient and the stateful memory.
 """
 from collections import defaultdict
 
@@ -44,7 +49,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib as L
-from .attn_op import AttnFn, TrainAttnFn, _as_dev
+from . import attn_layer as AL
+from .attn_layer import cat_rows as _cat_rows  # noqa: F401  (the name it had here: tests/test_tgn_cat_rows.py)
+from .attn_op import AttnFn, TrainAttnFn, as_dev
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -310,37 +317,17 @@ def _gathered_table_grad(spec, desc, slot_ab, gz, tab):
     return d_tab
 
 
-def _cat_rows(xs):
-    """torch.cat(xs) along dim 0 -- as a view when the tensors are consecutive row blocks of one contiguous
-    tensor (a gathered pack's three sides, [3, B, ...]), else a copy.  Only for tensors without autograd
-    history (the view would route gradients through the first one's base)."""
-    a = xs[0]
-    if all(isinstance(x, torch.Tensor) for x in xs) and not any(x.requires_grad for x in xs):
-        st = a.untyped_storage().data_ptr()
-        adjacent = all(x.is_contiguous() and x.dtype == a.dtype and x.device == a.device and x.dim() == a.dim()
-                       and x.shape[1:] == a.shape[1:] and x.untyped_storage().data_ptr() == st for x in xs)
-        if adjacent:
-            off = a.storage_offset()
-            for x in xs:
-                if x.storage_offset() != off:
-                    adjacent = False
-                    break
-                off += x.numel()
-        if adjacent:
-            # explicit contiguous strides: is_contiguous() ignores the stride of a size-1 dim, so a.stride()
-            # may not describe consecutive rows when a has one row
-            shape = (sum(int(x.shape[0]) for x in xs),) + tuple(a.shape[1:])
-            strides, acc = [], 1
-            for d in reversed(shape):
-                strides.append(acc)
-                acc *= int(d)
-            return a.as_strided(shape, tuple(reversed(strides)), a.storage_offset())
-    return torch.cat(list(xs))
-
-
 # ------------------------------------------------------------------ the model
-class TGN(nn.Module):
-    """TGN/tgn.py:14-97 constructor (same arguments, submodules and initialisation order)."""
+class TGN(AL.HipTraining, nn.Module):
+    """TGN/tgn.py:14-97 constructor (same arguments, submodules and initialisation order).
+
+    ``train_on_hip()`` (attn_layer.HipTraining) opts in to the HIP training step of the stateful path
+    (``forbidden_memory_update`` False): ``train()`` calls of contrast / get_node_emb / node_embeddings with
+    gradients enabled run tm_tgn_attn_train_fwd / tm_tgn_attn_train_bwd, and contrast / get_node_emb advance the
+    memory as tgn.py:167-191 does.  In ``eval()`` or under ``no_grad`` the stateful path needs no flag: it runs
+    without dropout and advances the memory the same way."""
+    _label = "TGN"
+    _param_error = "TGN with memory updates: parameters must be contiguous fp32 on the HIP device (model.to(device))"
 
     def __init__(self, n_feat, e_feat, n_neighbors, device=None, n_layers=2, n_heads=2, dropout=0.1,
                  use_memory=True, forbidden_memory_update=False, memory_update_at_start=True, message_dimension=100,
@@ -476,12 +463,7 @@ class TGN(nn.Module):
             for lay in self.embedding_module.attention_models[:2]:
                 mh = lay.multi_head_target
                 H, dk = mh.n_head, mh.d_k
-                wq = mh.w_qs.weight.detach().to(dev, torch.float64).view(H, dk, -1)     # [H, dk, dq]
-                wk = mh.w_ks.weight.detach().to(dev, torch.float64).view(H, dk, dk)     # [H, dk(out), dk(in)]
-                wv = mh.w_vs.weight.detach().to(dev, torch.float64).view(H, dk, dk)
-                fc = mh.fc.weight.detach().to(dev, torch.float64)                       # [dq, H*dk]
-                P = torch.einsum("hoi,hoq->hiq", wk, wq).reshape(H * dk, -1)             # W_k,h^T W_q,h
-                G = torch.einsum("qho,hoi->qhi", fc.view(fc.shape[0], H, dk), wv).reshape(fc.shape[0], H * dk)
+                P, G = AL.fold(mh, torch.float64, dev)              # row-major: _layer multiplies by their .t() views
                 layers.append(dict(
                     P=P.to(f32).contiguous(), G=G.to(f32).contiguous(), fcb=mh.fc.bias.detach().to(dev, f32),
                     lnw=mh.layer_norm.weight.detach().to(dev, f32), lnb=mh.layer_norm.bias.detach().to(dev, f32),
@@ -498,21 +480,6 @@ class TGN(nn.Module):
         return pack
 
     # -------------------------------------------------------------- the stateful path (tgn.py:100-199)
-    def train_on_hip(self, flag=True):
-        """Opt in to (or out of) the HIP training step: with the flag set and ``forbidden_memory_update`` False,
-        ``model.train()`` calls of contrast / get_node_emb / node_embeddings with gradients enabled run
-        tm_tgn_attn_train_fwd / tm_tgn_attn_train_bwd with the reference's two dropouts, ``loss.backward()``
-        fills ``.grad`` on every parameter the reference's step trains, and contrast / get_node_emb advance the
-        memory as tgn.py:167-191 does.  In ``eval()`` or under ``no_grad`` the stateful path needs no flag: it runs
-        without dropout and advances the memory the same way."""
-        self._train_on_hip = bool(flag)
-        self._live_checked = None
-        return self
-
-    def _apply(self, fn, *args, **kwargs):
-        self._live_checked = None          # .to() / .float() / ...: the parameters are looked at again
-        return super()._apply(fn, *args, **kwargs)
-
     def _stateful(self):
         """True when contrast / get_node_emb / node_embeddings update the memory (tgn.py:167); refuses the options
         the stateful path does not restate, naming the option."""
@@ -533,19 +500,6 @@ class TGN(nn.Module):
                                       "layers run)")
         return True
 
-    def _live_dev(self):
-        """The device of the stateful path, its parameters checked once."""
-        dev = self._dev()
-        if getattr(self, "_live_checked", None) != dev:       # once per train_on_hip() / .to(), not per step
-            for p in self.parameters():
-                if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("TGN with memory updates: parameters must be contiguous fp32 on the HIP "
-                                       "device (model.to(device))")
-            self._live_checked = dev
-        if getattr(self, "_live_err", None) is None or self._live_err.device != dev:
-            self._live_err = torch.zeros(1, dtype=torch.int32, device=dev)
-        return dev
-
     def _raw_dim(self):
         return 2 * self.memory_dimension + self.n_edge_features + self.time_encoder.dimension
 
@@ -560,11 +514,7 @@ class TGN(nn.Module):
     def draw_keep_masks(self, R1, N, generator=None):
         """One step's keep masks (uint8, 1 = kept with probability 1 - dropout), drawn on the device in one
         ``bernoulli_``: [attention layer 0, attention layer 1, fc layer 0, fc layer 1]."""
-        shapes = self.keep_mask_shapes(R1, N)
-        sizes = [int(np.prod(sh)) for sh in shapes]
-        flat = torch.empty(sum(sizes), dtype=torch.uint8, device=self._dev()).bernoulli_(
-            1.0 - float(self.embedding_module.dropout), generator=generator)
-        return [x.view(sh) for x, sh in zip(flat.split(sizes), shapes)]
+        return AL.draw_keep_masks(self.keep_mask_shapes(R1, N), self.embedding_module.dropout, self._dev(), generator)
 
     def _updated_state(self, dev):
         """get_updated_memory(all nodes, messages) (tgn.py:241-252) from the device store: M' = memory with
@@ -596,33 +546,21 @@ class TGN(nn.Module):
         mh = lay.multi_head_target
         H, dk = mh.n_head, mh.d_k
         dn = self.n_node_features
-        dq = 2 * dn
         if H > 4:
             raise NotImplementedError(f"n_heads {H}: the attention kernels hold at most 4 heads")
         if tab.requires_grad:
-            src = _GatherRowsFn.apply(tab, src_idx, self._live_err)
+            src = _GatherRowsFn.apply(tab, src_idx, self._train_err)
         else:
             src = tab.index_select(0, src_idx)
         query = torch.cat([src, cosb.expand(R, dn)], dim=1)                           # [R, dq]
-        wq = mh.w_qs.weight.view(H, dk, dq)
-        wk, wv = mh.w_ks.weight.view(H, dk, dk), mh.w_vs.weight.view(H, dk, dk)
-        P = torch.einsum("hoi,hoq->hiq", wk, wq).reshape(H * dk, dq)                   # W_k,h^T W_q,h
-        G = torch.einsum("qho,hoi->qhi", mh.fc.weight.view(dq, H, dk), wv).reshape(dq, H * dk)
+        P, G = AL.fold(mh)
         qf = (query @ P.t()).contiguous()
-        de = edge_dense.shape[-1] if edge_dense is not None else self.n_edge_features
-        if dn + de + dn != dk:
-            raise AssertionError(f"key dim {dn}+{de}+{dn} != {dk}")
-        spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=dn, d_edge=de, d_time=dn,
-                    node_rows=tab.shape[0], edge_rows=self.e_feat_th.shape[0], head_major=self.head_major_rows,
-                    temperature=mh.temperature, node_idx=node_idx,
-                    edge_tab=edge_dense if edge_dense is not None else self.e_feat_th,
-                    edge_idx=None if edge_dense is not None else edge_idx, dt=dt, mask_node=mask_node,
-                    err=self._live_err, seg_rows=seg, flavour="tgn", table_grad=_gathered_table_grad)
+        spec = AL.attn_spec("tgn", R, N, H, dk, dn, dn, mh.temperature, self.head_major_rows, seg, node_tab=tab,
+                            node_idx=node_idx, edge_tab=self.e_feat_th, edge_idx=edge_idx, edge_dense=edge_dense,
+                            dt=dt, mask_node=mask_node, err=self._train_err, table_grad=_gathered_table_grad)
         z = TrainAttnFn.apply(qf, ngh_dense, None if ngh_dense is not None else tab, tw, tb, spec, akeep, scale)
-        out = torch.addmm(mh.fc.bias, z, G.t())
-        if fkeep is not None:
-            out = out * (fkeep.to(out.dtype) * scale)                  # fc's dropout (embedding_module.py:84)
-        h = F.layer_norm(out + query, (dq,), mh.layer_norm.weight, mh.layer_norm.bias, 1e-5)
+        # fc's dropout: embedding_module.py:84
+        h = AL.mha_tail(z, query, G.t(), mh.fc.bias, mh.layer_norm.weight, mh.layer_norm.bias, fkeep, scale)
         return lay.merger(h, src)
 
     def _embed_live(self, x, st, explain_weights=None, edge_attr=None):
@@ -632,42 +570,32 @@ class TGN(nn.Module):
             raise NotImplementedError("TGN with memory updates: explain_weights (the explainer runs on the frozen "
                                       "model, forbidden_memory_update=True)")
         train = self.training and torch.is_grad_enabled()
-        if train and not getattr(self, "_train_on_hip", False):
+        if train and not self._train_on_hip:
             raise NotImplementedError("TGN in train() mode with memory updates: call model.train_on_hip() first "
                                       "(the HIP training step is opt-in; eval() / no_grad need no flag)")
-        R1, N, seg1 = x["R1"], x["N"], x["seg1"]
+        R1, N, seg1 = x["R"], x["N"], x["seg"]
         p = float(self.embedding_module.dropout) if train else 0.0
-        dev = st["M"].device
-        keep = getattr(self, "tgn_keep_masks", None) if train else None
-        if keep is None and p > 0.0:
-            keep = self.draw_keep_masks(R1, N)
-        if keep is not None:
-            shapes = self.keep_mask_shapes(R1, N)
-            if len(keep) != 4 or any(k.dtype != torch.uint8 or k.device != dev or k.numel() != int(np.prod(sh))
-                                     for k, sh in zip(keep, shapes)):
-                raise ValueError("TGN.tgn_keep_masks: expected draw_keep_masks(R1, N)'s four uint8 masks on the device")
-            keep = [k.contiguous().view(sh) for k, sh in zip(keep, shapes)]
-        else:
-            keep = [None] * 4
-        scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
+        keep, scale = AL.step_keep_masks(
+            getattr(self, "tgn_keep_masks", None) if train else None, self.keep_mask_shapes(R1, N), p, st["M"].device,
+            "TGN.tgn_keep_masks: expected draw_keep_masks(R1, N)'s four uint8 masks on the device")
         tab = (st["M"] + self.n_feat_th).contiguous()
         te = self.time_encoder
         tw, tb = te.w.weight.view(-1), te.w.bias
         cosb = torch.cos(tb)
         lay0, lay1 = self.embedding_module.attention_models[0], self.embedding_module.attention_models[1]
         # layer 0: hop-1 nodes attend over their hop-2 neighbours, keys gathered from tab
-        y0 = self._layer_live(lay0, tab, x["n1l"], R1 * N, N, x["n2f"], None, x["e2"], x["ed2"], x["dt2"], x["n2f"],
+        y0 = self._layer_live(lay0, tab, x["n1l"], R1 * N, N, x["n2"], None, x["e2"], x["ed2"], x["dt2"], x["n2"],
                               seg1 * N, keep[0], keep[2], scale, tw, tb, cosb)
         # layer 1: roots attend over the hop-1 embeddings
         y1 = self._layer_live(lay1, tab, x["n0"], R1, N, None, y0.contiguous(), x["e1"], x["ed1"], x["dt1"],
-                              x["n1f"], seg1, keep[1], keep[3], scale, tw, tb, cosb)
+                              x["n1"], seg1, keep[1], keep[3], scale, tw, tb, cosb)
         self._tgn_train_key = (R1, N, keep[0] is not None)   # marker: the stateful path ran
         return y1
 
     def _stateful_embed(self, x, src_idx, tgt_idx, cut_time, e_idx, explain_weights=None, edge_attr=None):
         """get_node_emb with memory updates (tgn.py:123-196): embeddings over the updated memory, then the state
         moves on with this step's values (no gradient flows into the stored state)."""
-        dev = self._live_dev()
+        dev = self._live_state(self._dev())
         st = self._updated_state(dev)
         emb = self._embed_live(x, st, explain_weights, edge_attr)
         if len(src_idx) > 0:
@@ -685,8 +613,8 @@ class TGN(nn.Module):
         if e_idx is None:
             raise ValueError("TGN with memory updates: e_idx is needed for the raw messages")
         B, n = len(src_idx), self.n_nodes
-        src = _as_dev(src_idx, dev, torch.long).reshape(-1)
-        dst = _as_dev(tgt_idx, dev, torch.long).reshape(-1)
+        src = as_dev(src_idx, dev, torch.long).reshape(-1)
+        dst = as_dev(tgt_idx, dev, torch.long).reshape(-1)
         pos = torch.cat([src, dst])
         vals, order = torch.sort(pos, stable=True)
         ar = torch.arange(n, dtype=torch.long, device=dev)
@@ -698,9 +626,9 @@ class TGN(nn.Module):
         mem.memory.data = torch.where(apply.unsqueeze(1), M, mem.memory.data)
         mem.last_update.data = torch.where(apply, mem.msg_ts, mem.last_update.data)
         # get_raw_messages (:254-278) with the just updated last_update and ts cast to fp32
-        ts = _as_dev(cut_time, dev, torch.float64).reshape(-1)[:B].float()
+        ts = as_dev(cut_time, dev, torch.float64).reshape(-1)[:B].float()
         lu = mem.last_update.data
-        ef = self.e_feat_th.index_select(0, _as_dev(e_idx, dev, torch.long).reshape(-1))
+        ef = self.e_feat_th.index_select(0, as_dev(e_idx, dev, torch.long).reshape(-1))
         w64, b64 = self.time_encoder.w.weight.detach().view(1, -1).double(), self.time_encoder.w.bias.detach().double()
 
         def tenc(delta):
@@ -795,18 +723,12 @@ class TGN(nn.Module):
             if cache is not None:
                 cache[key] = (pk, query, qf)
         src_feat = query[:, :dn]
-        de = edge_dense.shape[-1] if edge_dense is not None else self.n_edge_features
-        if dn + de + dn != dk:
-            raise AssertionError(f"key dim {dn}+{de}+{dn} != {dk}")
-        spec = dict(rows=R, n_ngh=N, n_head=H, d_key=dk, d_node=dn, d_edge=de, d_time=dn,
-                    node_rows=pk["tab"].shape[0], edge_rows=pk["etab"].shape[0], head_major=self.head_major_rows,
-                    temperature=lw["temperature"], node_tab=pk["tab"], node_idx=node_idx,
-                    edge_tab=edge_dense if edge_dense is not None else pk["etab"],
-                    edge_idx=None if edge_dense is not None else edge_idx, dt=dt, time_w=pk["tw"],
-                    time_b=pk["tb"], mask_node=mask_node, err=pk["err"], seg_rows=seg, flavour="tgn")
+        spec = AL.attn_spec("tgn", R, N, H, dk, dn, dn, lw["temperature"], self.head_major_rows, seg,
+                            node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"], edge_idx=edge_idx,
+                            edge_dense=edge_dense, dt=dt, time_w=pk["tw"], time_b=pk["tb"], mask_node=mask_node,
+                            err=pk["err"])
         z = AttnFn.apply(qf, ngh_dense, ew, spec)
-        out = torch.addmm(lw["fcb"], z, lw["G"].t())
-        h = F.layer_norm(out + query, (query.shape[1],), lw["lnw"], lw["lnb"], 1e-5)
+        h = AL.mha_tail(z, query, lw["G"].t(), lw["fcb"], lw["lnw"], lw["lnb"])
         x = torch.cat([h, src_feat], dim=1)
         return F.linear(F.relu(F.linear(x, lw["m1w"], lw["m1b"])), lw["m2w"], lw["m2b"])
 
@@ -822,10 +744,10 @@ class TGN(nn.Module):
             x = prepared if prepared is not None else self._prep_inputs(nodes, eids, times, cut_time, edge_attr,
                                                                         n_segments)
             # no events here: the embeddings over the updated memory, the state left as it is
-            return self._embed_live(x, self._updated_state(self._live_dev()), explain_weights, edge_attr)
+            return self._embed_live(x, self._updated_state(self._live_state(self._dev())), explain_weights, edge_attr)
         pk = self._pack()
         x = prepared if prepared is not None else self._prep_inputs(nodes, eids, times, cut_time, edge_attr, n_segments)
-        R1, N, seg1 = x["R1"], x["N"], x["seg1"]
+        R1, N, seg1 = x["R"], x["N"], x["seg"]
         dev = pk["dev"]
         ew1 = ew2 = None
         if explain_weights is not None:
@@ -834,53 +756,19 @@ class TGN(nn.Module):
         tab = pk["tab"]
         # layer 0 (attention_models[0]): hop-1 nodes attend over their hop-2 neighbours
         cache = x if prepared is not None else None
-        y0 = self._layer(pk, 0, lambda: tab[x["n1l"]], R1 * N, N, x["n2f"], None, x["e2"], x["ed2"], x["dt2"],
-                         x["n2f"], ew2, seg1 * N, cache)
+        y0 = self._layer(pk, 0, lambda: tab[x["n1l"]], R1 * N, N, x["n2"], None, x["e2"], x["ed2"], x["dt2"],
+                         x["n2"], ew2, seg1 * N, cache)
         # layer 1 (attention_models[1]): roots attend over the hop-1 embeddings
         y1 = self._layer(pk, 1, lambda: tab[x["n0"]], R1, N, None, y0.contiguous(), x["e1"], x["ed1"], x["dt1"],
-                         x["n1f"], ew1, seg1, cache)
+                         x["n1"], ew1, seg1, cache)
         return y1
 
     def _prep_inputs(self, nodes, eids, times, cut_time, edge_attr=None, n_segments=1):
         """node_embeddings' index, time-offset and edge-attribute tensors (retrieve_time_features etc.)."""
-        dev = self._dev()
-        i32 = torch.int32
-        n0 = _as_dev(nodes[0], dev, torch.long).reshape(-1)
-        R1 = n0.shape[0]
-        n1 = _as_dev(nodes[1], dev, i32).reshape(R1, -1)
-        N = n1.shape[1]
-        n2 = _as_dev(nodes[2], dev, i32).reshape(R1 * N, N)
-        cut = _as_dev(cut_time, dev, torch.float64).reshape(-1)
-        if cut.shape[0] * 3 * n_segments == R1:
-            cut = cut.repeat(3 * n_segments)
-        if cut.shape[0] != R1 or R1 % n_segments:
-            raise AssertionError("cut_time must give one time per event (or per root row)")
-        seg1 = R1 // n_segments if n_segments > 1 else 0
-        t1 = _as_dev(times[0], dev, torch.float64).reshape(R1, N)
-        t2 = _as_dev(times[1], dev, torch.float64).reshape(R1, N, N)
-        dt1 = (cut.view(R1, 1) - t1).float().contiguous()                     # retrieve_time_features
-        dt2 = (t1.view(R1, N, 1) - t2).float().contiguous()
-        if edge_attr is None:
-            e1 = _as_dev(eids[0], dev, i32).reshape(-1).contiguous()
-            e2 = _as_dev(eids[1], dev, i32).reshape(-1).contiguous()
-            ed1 = ed2 = None
-        else:
-            if any(isinstance(x, torch.Tensor) and x.requires_grad for x in edge_attr):
-                raise NotImplementedError("gradient with respect to edge_attr")
-            e1 = e2 = None
-            ed1 = _as_dev(edge_attr[0], dev, torch.float32).reshape(R1 * N, -1).contiguous()
-            ed2 = _as_dev(edge_attr[1], dev, torch.float32).reshape(R1 * N * N, -1).contiguous()
-        return dict(R1=R1, N=N, seg1=seg1, n0=n0, n1l=n1.reshape(-1).long(), n1f=n1.reshape(-1).contiguous(),
-                    n2f=n2.reshape(-1).contiguous(), dt1=dt1.reshape(-1), dt2=dt2.reshape(-1), e1=e1, e2=e2,
-                    ed1=ed1, ed2=ed2)
-
-    def check_errors(self):
-        """Raise if a kernel saw an out-of-range node or edge index (synchronises)."""
-        pk = self._pack_cache
-        for err in ((pk or {}).get("err"), getattr(self, "_live_err", None)):
-            if err is not None and int(err.item()) != 0:
-                err.zero_()
-                raise IndexError("TGN: node or edge index out of range of the feature tables")
+        x = AL.prep_inputs(self._dev(), nodes, eids, times, cut_time, n_segments, sides=3, lone_seg_rows=False,
+                           edge_attr=edge_attr)
+        x["n1l"] = x["n1"].long()          # the hop-1 nodes as layer 0's source rows (an index into the table)
+        return x
 
     # -------------------------------------------------------------- reference API
     def get_node_emb(self, src_idx, tgt_idx, bgd_idx, cut_time, e_idx, subgraph_src, subgraph_tgt, subgraph_bgd,
@@ -904,25 +792,12 @@ class TGN(nn.Module):
         """The inputs contrast derives from its batch (the three sides' roots and subgraphs
         concatenated, time offsets), built once: the training step's two contrasts of the same batch
         (without and with explanation weights, temp_exp_main.py:597, :611) share them."""
-        dev = self._dev()
-        roots = torch.cat([_as_dev(x, dev, torch.long).reshape(-1) for x in (src_idx, tgt_idx, bgd_idx)])
-
-        def cat(i, h, dtype):
-            xs = [sg[i][h] for sg in (subgraph_src, subgraph_tgt, subgraph_bgd)]
-            if all(isinstance(x, torch.Tensor) and x.device == dev for x in xs):
-                # the three sides of a gathered pack are consecutive rows of one tensor: one view, and one
-                # dtype conversion instead of three (elementwise, so the same values as convert-then-cat)
-                return _as_dev(_cat_rows(xs), dev, dtype)
-            return torch.cat([_as_dev(x, dev, dtype) for x in xs])
-        nodes = [roots, cat(0, 0, torch.int32), cat(0, 1, torch.int32)]
-        eids = [cat(1, 0, torch.int32), cat(1, 1, torch.int32)] if edge_attr is None else [None, None]
-        times = [cat(2, 0, torch.float64), cat(2, 1, torch.float64)]
-        return self._prep_inputs(nodes, eids, times, cut_time, edge_attr)
+        roots, nodes, eids, times = AL.stack_sides(self._dev(), (src_idx, tgt_idx, bgd_idx),
+                                                   (subgraph_src, subgraph_tgt, subgraph_bgd), eids=edge_attr is None)
+        return self._prep_inputs([roots] + nodes, eids, times, cut_time, edge_attr)
 
     def affinity(self, x1, x2):
-        pk = self._pack()
-        h = F.relu(F.linear(torch.cat([x1, x2], dim=1), pk["a1w"], pk["a1b"]))
-        return F.linear(h, pk["a2w"], pk["a2b"])
+        return AL.affinity(self._pack(), x1, x2)
 
     def contrast(self, src_idx, tgt_idx, bgd_idx, cut_time, e_idx, subgraph_src, subgraph_tgt, subgraph_bgd,
                  explain_weights=None, edge_attr=None, prepared=None):
@@ -954,7 +829,7 @@ class TGN(nn.Module):
         et = self._pack()["etab"]
         out = []
         for h in (0, 1):
-            idx = torch.cat([_as_dev(sg[1][h], dev, torch.long) for sg in (subgraph_src, subgraph_tgt, subgraph_bgd)])
+            idx = torch.cat([as_dev(sg[1][h], dev, torch.long) for sg in (subgraph_src, subgraph_tgt, subgraph_bgd)])
             out.append(et[idx])
         return out
 
@@ -972,7 +847,7 @@ class TGN(nn.Module):
 
 def node_records_cat(subgraph, dev):
     """[hop-1 | hop-2] node records of one side as one int32 device tensor [B, N + N^2]."""
-    return torch.cat([_as_dev(subgraph[0][0], dev, torch.int32), _as_dev(subgraph[0][1], dev, torch.int32)], dim=1)
+    return torch.cat([as_dev(subgraph[0][0], dev, torch.int32), as_dev(subgraph[0][1], dev, torch.int32)], dim=1)
 
 
 __all__ = ["TGN", "TimeEncode", "MergeLayer", "TemporalAttentionLayer", "MultiHeadAttention", "Memory",

@@ -30,6 +30,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .attn_op import as_dev
 
 SIDES = ("src", "tgt", "bgd")
 
@@ -106,12 +107,6 @@ def _batch(src, dst, ts, e_idx, fake, node6, eid3, ts3, cat, cnt, s1, s2):
     return b
 
 
-def _as_dev(x, dev, dtype):
-    if isinstance(x, torch.Tensor):
-        return x.to(dev, dtype)
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev, dtype)
-
-
 def encode_sides(explainer, batch):
     """TempME.forward for the src / tgt / bgd walks of one batch (temp_exp_main.py:605-607).  On the HIP
     path the three sides go through ONE forward_groups call (one std group per side, exactly as three
@@ -120,12 +115,12 @@ def encode_sides(explainer, batch):
         return [explainer(w, batch.ts, e) for w, e in zip(batch.walks, batch.edges)]
     dev = explainer._dev()
     if batch.stacked is None:
-        st = lambda k, dt: torch.stack([_as_dev(w[k], dev, dt) for w in batch.walks])  # noqa: E731
-        cnt = torch.stack([_as_dev(e, dev, torch.float32) for e in batch.edges])
+        st = lambda k, dt: torch.stack([as_dev(w[k], dev, dt) for w in batch.walks])  # noqa: E731
+        cnt = torch.stack([as_dev(e, dev, torch.float32) for e in batch.edges])
         batch.stacked = (st(0, torch.int32), st(1, torch.int32), st(2, torch.float32), st(3, torch.int32), cnt)
     node6, eid3, ts3, cat, cnt = batch.stacked
     G, B, W = node6.shape[0], node6.shape[1], node6.shape[2]
-    cut = _as_dev(batch.ts, dev, torch.float64).reshape(1, B).expand(G, B)
+    cut = as_dev(batch.ts, dev, torch.float64).reshape(1, B).expand(G, B)
     imp = explainer.forward_groups(node6, eid3, ts3, cat.reshape(G, B, W), cut, cnt, G, B, W)
     sides = list(imp.view(G, B, W, 1).unbind(0))
     batch.imp_all = (imp, sides)      # the three sides' importances as one tensor (explain_sides, kl_loss)
@@ -265,10 +260,10 @@ def explain_sides(explainer, batch, imps, training):
     if ss is not None and all(x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() for x in ss):
         s1n, s1e, s2n, s2e = ss
     else:
-        s1n = torch.stack([_as_dev(sg[0][0], dev, torch.int32) for sg in batch.subgraphs])
-        s1e = torch.stack([_as_dev(sg[1][0], dev, torch.int32) for sg in batch.subgraphs])
-        s2n = torch.stack([_as_dev(sg[0][1], dev, torch.int32) for sg in batch.subgraphs])
-        s2e = torch.stack([_as_dev(sg[1][1], dev, torch.int32) for sg in batch.subgraphs])
+        s1n = torch.stack([as_dev(sg[0][0], dev, torch.int32) for sg in batch.subgraphs])
+        s1e = torch.stack([as_dev(sg[1][0], dev, torch.int32) for sg in batch.subgraphs])
+        s2n = torch.stack([as_dev(sg[0][1], dev, torch.int32) for sg in batch.subgraphs])
+        s2e = torch.stack([as_dev(sg[1][1], dev, torch.int32) for sg in batch.subgraphs])
     N = s1n.shape[-1]
     imp = _stacked_imp(batch, imps, G, B, W)
     e1, e2 = explainer.explain_groups(imp, eid3, ts3, s1n, s1e, s2n, s2e, G, B, W, N, training)

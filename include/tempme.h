@@ -771,6 +771,28 @@ int tm_mask_least_important(const float *imp, int32_t rows, int32_t n, const int
 int tm_rank_metrics(const float *score, int64_t score_stride, const float *label, int64_t label_stride,
                     int32_t n_vec, int32_t n, double *out, void *stream);
 
+/* Ranked explanation edges: the distinct edges behind a prediction, best first, from the per-slot explanation
+ * weights of retrieve_explanation (explainer_new.py:408-418; the reference's visualize_explanations.py stops at
+ * heat maps of the slot weights).  imp1 [rows, n] / imp2 [rows, n*n] with their node and edge-id records of the same
+ * shapes (imp2 / node2 / eid2 NULL when hops == 1, a GraphMixer base); an entry is live iff its node record is
+ * nonzero and its edge id positive.  group_rows [n_groups, rows_per_group] (1 or 2 rows, -1 = no row) names each
+ * group's rows; its entries are their slots in that order: entry p * ne + s for position p and slot s, hop-1 slots
+ * first, ne = n (hops 1) or n + n*n (hops 2).  Per group, every distinct edge id among the live entries once:
+ *   score = the maximum over the edge's live entries (fp32 comparison, -0 == +0, a NaN loses to every number; the
+ *           stored bits are that entry's, except that a zero maximum is +0.0 and an all-NaN one 0x7FC00000)
+ *   slot  = the edge's lowest live entry index        mult = the number of its live entries
+ * ordered by score descending (NaN last), equal scores by edge id ascending.  out_* [n_groups, k] hold the first k;
+ * positions j >= min(count, k) hold eid 0, score 0, slot -1, mult 0; out_count [n_groups] = the distinct live edges
+ * (may exceed k).  Comparisons only, no atomics: the same bits from every launch.
+ * A group_rows value outside [-1, rows) sets *err_flag (nullable device int32) to TM_E_ARG and counts as no row.
+ * rows_per_group * ne > 8192: TM_E_UNSUPPORTED; k < 1 or k > rows_per_group * ne, hops / rows_per_group outside
+ * their values, n < 1: TM_E_ARG; n_groups = 0 is a no-op. */
+int tm_ranked_edges(const float *imp1, const float *imp2, const int32_t *node1, const int32_t *node2,
+                    const int32_t *eid1, const int32_t *eid2, int32_t rows, int32_t n, int32_t hops,
+                    const int32_t *group_rows, int32_t n_groups, int32_t rows_per_group, int32_t k, int32_t *out_eid,
+                    float *out_score, int32_t *out_slot, int32_t *out_mult, int32_t *out_count, int32_t *err_flag,
+                    void *stream);
+
 /* ---------------------------------------------------------------- per-kernel timing
  * tm_profile_enable(1) clears and starts recording a HIP event pair around every kernel
  * launch, on that launch's stream; tm_profile_sync() waits and aggregates, returning the

@@ -212,7 +212,7 @@ def cat_rows(xs):
     return torch.cat(list(xs))
 
 
-def stack_sides(dev, roots, subgraphs, nodes=True, eids=True, hops=2, idx_dtype=torch.int32):
+def stack_sides(dev, roots, subgraphs, nodes=True, eids=True, hops=2, idx_dtype=torch.int32, times=True):
     """The sides of a contrast stacked along dim 0 -> (n0 [S B] int64, node ids, edge ids, times), each of the
     three a list of ``hops`` tensors ([S B, N], [S B, N^2]) in idx_dtype / fp64, or None where not asked for.
     ``subgraphs``: per side (node ids, edge ids, times), each a list over hops."""
@@ -229,7 +229,8 @@ def stack_sides(dev, roots, subgraphs, nodes=True, eids=True, hops=2, idx_dtype=
             else:
                 out.append(torch.cat([as_dev(x, dev, dtype) for x in xs]))
         return out
-    return (n0, cat(0, idx_dtype) if nodes else None, cat(1, idx_dtype) if eids else None, cat(2, torch.float64))
+    return (n0, cat(0, idx_dtype) if nodes else None, cat(1, idx_dtype) if eids else None,
+            cat(2, torch.float64) if times else None)
 
 
 __all__ = ["fold", "attn_spec", "mha_tail", "affinity", "draw_keep_masks", "checked_keep_masks", "step_keep_masks",

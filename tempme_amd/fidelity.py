@@ -94,6 +94,24 @@ def masked_contrast_tgat(base_model, explanation, *batch):
     return masked_contrast(base_model, stacked, *batch, side_segments=True)
 
 
+def kept_edges(args, explanation, subgraph_src, subgraph_tgt, subgraph_bgd, roots, ratio, k, pairs=True):
+    """The ranked edges (ranked_edges.RankedEdges) of exactly the subgraph ``threshold_test`` scores at sparsity
+    ``ratio``: the entries ``_masked_nodes`` keeps for that ratio are the live ones, no other selection rule.
+    ``roots``: (src_l_cut, dst_l_cut, dst_l_fake); ``explanation`` as threshold_test takes it for args.base_type."""
+    from .ranked_edges import _stack_explanation, ranked_edges
+    if args.base_type not in ("tgn", "graphmixer", "tgat"):
+        raise NotImplementedError(f"kept_edges for base_type {args.base_type!r}: tgn, graphmixer and tgat are built")
+    ex0 = explanation[0]
+    if not torch.is_tensor(ex0):
+        raise TypeError("kept_edges: explanation is a list of torch tensors")
+    dev = L.require_device(ex0.device)
+    hops = 1 if args.base_type == "graphmixer" else 2
+    imp = _stack_explanation(explanation, dev)[:hops]
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    masked = _masked_nodes(imp, sgs, args.n_degree, [ratio], dev, hops=hops)[0]
+    return ranked_edges(imp, sgs, roots, k, pairs=pairs, node_records=masked)
+
+
 def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, e_l_cut,
                    pos_out_ori, neg_out_ori, y_ori, subgraph_src, subgraph_tgt, subgraph_bgd, device_metrics=False):
     """temp_exp_main.py:153-272 -> (aps_AUC, auc_AUC, acc_AUC, fid_prob_AUC, fid_logit_AUC): five floats, or with

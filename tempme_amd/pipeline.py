@@ -125,6 +125,7 @@ class ExplainPipeline:
 
     def sample(self, src, dst, ts, eidx, event_ids):
         self._alloc(int(src.numel()))
+        self._roots = (src, dst)
         return sample_events(self.graph, self.seed, self.split, self.N, self.M, src, dst, ts, eidx, event_ids,
                              self.dst_list, out=self.buf, check=False)
 
@@ -170,6 +171,20 @@ class ExplainPipeline:
         E, N, W = self._E, self.N, self.W
         return self.imp[:3 * E * W].view(3, E, W), self.h1[:3 * E * N].view(3, E, N), \
             self.h2[:3 * E * N * N].view(3, E, N * N)
+
+    def ranked_edges(self, k, pairs=True):
+        """The distinct edges behind each of the last call's predictions, best first (ranked_edges.RankedEdges),
+        from the pipeline's own buffers after ``run()``: [2, E, k] with ``pairs`` (prediction (0, i) merges event
+        i's src and tgt rows, (1, i) its src and bgd rows), else [3E, k].  One launch on the current stream."""
+        from .ranked_edges import ranked_edges
+        if self._E is None or getattr(self, "_roots", None) is None:
+            raise RuntimeError("ExplainPipeline.ranked_edges: nothing has run yet")
+        E, N, b = self._E, self.N, self.buf
+        sgs = [([b.sub1_node[s], b.sub2_node[s]], [b.sub1_eid[s], b.sub2_eid[s]], [b.sub1_ts[s], b.sub2_ts[s]])
+               for s in range(3)]
+        src, dst = self._roots
+        return ranked_edges([self.h1[:3 * E * N].view(3 * E, N), self.h2[:3 * E * N * N].view(3 * E, N * N)], sgs,
+                            (src, dst, b.dst_fake[:E]), k, pairs=pairs)
 
     def check_errors(self):
         if getattr(self, "buf", None) is not None:   # nothing sampled yet: nothing to report

@@ -2880,7 +2880,7 @@ static int encoder_forward(const EncFwd &c) {
         !c.out || (c.pool && !c.wgt))
         return refuse(TM_E_ARG, c.who, "NULL pointer");
     // (the pooled training forward is the one that also asks about its head tile)
-    if (gcn_lds(P) > 160 * 1024 || (c.pool && c.train && (head_lds(P) > 160 * 1024 || P.h > 256)))
+    if (gcn_lds(P) > LDS_BUDGET || (c.pool && c.train && (head_lds(P) > LDS_BUDGET || P.h > 256)))
         return refuse(TM_E_UNSUPPORTED, c.who, "feature dims too large for LDS tile");
     hipStream_t s = S_(c.stream);
     const EncWs ws = enc_ws(c.w, n_walks, c.workspace);
@@ -2986,7 +2986,7 @@ extern "C" int tm_edge_importance(const tm_weights *w, const float *e_feat, int3
     const EncW &P = w->P;
     const size_t lds = gate_lds(P);
     const size_t hlds = 2 * sizeof(int32_t) * (1u << hbits);
-    if (lds > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_edge_importance: LDS budget exceeded");
+    if (lds > LDS_BUDGET) return fail(TM_E_UNSUPPORTED, "tm_edge_importance: LDS budget exceeded");
     const int64_t n_pos = rows * 3 * W;
     float *wv = static_cast<float *>(scratch(sizeof(float) * (size_t)n_pos, S_(stream)));
     if (!wv) return fail(TM_E_HIP, "tm_edge_importance: scratch allocation failed");
@@ -3275,7 +3275,7 @@ extern "C" int tm_dropin_forward(tm_dropin *d, int32_t k, int32_t sync, const tm
     if (int rc = encoder_forward(fwd)) return rc;
     if (out_gfac && !fused_gate) {
         const size_t lds = gate_lds(P);
-        if (lds > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_dropin_forward: LDS budget exceeded");
+        if (lds > LDS_BUDGET) return fail(TM_E_UNSUPPORTED, "tm_dropin_forward: LDS budget exceeded");
         hipEvent_t pe = prof_begin(side);
         const unsigned rblocks = (unsigned)((n_pos + 63) / 64);
         // cached: the hits have their factor (the lookup), the misses (listed) run the register gate and fill the

@@ -10,6 +10,7 @@ namespace tmk {
 
 constexpr int HID = 64;   // hid_dim supported by this build (reference default --hid_dim 64)
 constexpr int TILE_ROWS = 32;
+constexpr size_t LDS_BUDGET = 160 * 1024;   // bytes of LDS one workgroup may ask for (a CDNA4 CU's 160 KB)
 
 __host__ __device__ constexpr int r16(int x) { return (x + 15) & ~15; }
 

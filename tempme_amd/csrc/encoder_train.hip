@@ -20,6 +20,7 @@
 // gradient, a column of ones appended to X) over all rows in two launches (tm_encoder_wgrad).
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "encoder_common.h"
 
@@ -1715,73 +1716,156 @@ void train_packs_free(tm_weights *w) {
     w->tbuf = nullptr;
 }
 
+static int refuse(int code, const char *who, const char *what) { return fail(code, std::string(who) + ": " + what); }
+
+// The training kernels' LDS sizes, each stated once.
 // walks per head_bwd_kernel workgroup: 16 (0 = the tiles exceed the LDS).  32-walk workgroups (110 KB of LDS at
 // hid_dim 64: one per CU) ran 0.224 ms per launch, 16-walk ones (55 KB, two per CU) 0.175 (round 5,
 // profiles/r05_train_tiles_ab.txt)
 static int head_bwd_tr(const EncW &P) {
-    return sizeof(float) * head_bwd_lds_floats(P.h, P.hm, 16) <= 160 * 1024 ? 16 : 0;
+    return sizeof(float) * head_bwd_lds_floats(P.h, P.hm, 16) <= LDS_BUDGET ? 16 : 0;
 }
 static size_t gcn_bwd_lds(const EncW &P) {
     const int ldx = r16(P.kev) + 8, ldab = r16(P.dn) + 8, ldh = r16(P.h) + 8;
     const size_t xsz = std::max(TILE_ROWS * ldx, 2 * TILE_ROWS * ldh);
     return sizeof(float) * (xsz + 2 * TILE_ROWS * ldab + 2 * TILE_ROWS * ldh) + 2 * TILE_ROWS * r16(P.dn);
 }
+// the gate's tiles: G1 [32][r16(h) + 8] and G2 [32][r16(h / 2) + 8]; the forward's X [32][r16(kdep) + 8] before them
+static size_t gate_bwd_lds(const EncW &P) { return sizeof(float) * TILE_ROWS * (r16(P.h) + 8 + r16(P.h / 2) + 8); }
+static size_t gate_fwd_lds(const EncW &P) { return sizeof(float) * TILE_ROWS * (r16(P.kdep) + 8) + gate_bwd_lds(P); }
+// What tm_encoder_bwd and tm_encoder_pool_bwd refuse on, and tm_encoder_train_supported asks.  The pooled call
+// asks about the plain head tile too (head_bwd_tr, the larger one), so the two calls take the same dims.
+static bool enc_bwd_fits(const EncW &P) { return P.h % 16 == 0 && head_bwd_tr(P) && gcn_bwd_lds(P) <= LDS_BUDGET; }
 
 // Whether the training kernels (tm_encoder_train_fwd / _bwd, tm_explain_train_fwd / _bwd) have an
 // instance for these encoder dims: hid_dim a multiple of 16 up to 256 whose tiles fit the LDS.
 extern "C" int tm_encoder_train_supported(int32_t de, int32_t dn, int32_t h, int32_t cat) {
     if (de <= 0 || dn <= 0 || h <= 0 || h % 16 || h > 256) return 0;
     EncW P{};
-    P.de = de;
-    P.dn = dn;
-    P.kev = de + 3 + dn;
-    P.kdep = de + dn;
-    P.h = h;
-    P.hm = cat ? h + 12 : h;
-    const size_t lim = 160 * 1024;
-    const size_t gate = sizeof(float) * TILE_ROWS * (r16(P.kdep) + 8 + r16(h) + 8 + r16(h / 2) + 8);
-    return head_bwd_tr(P) && gcn_bwd_lds(P) <= lim && gate <= lim ? 1 : 0;
+    P.de = de, P.dn = dn, P.kev = de + 3 + dn, P.kdep = de + dn, P.h = h, P.hm = cat ? h + 12 : h;
+    return enc_bwd_fits(P) && gate_fwd_lds(P) <= LDS_BUDGET ? 1 : 0;
 }
 
-// the register-resident event_gcn backward runs (the dims it has an instance for; the LDS-tiled one otherwise)
-static bool gcn_bwd_uses_reg(const tm_weights *w) {
-    const EncW &P = w->P;
+// The register-resident event_gcn instances gcn_fwd_reg_kernel / gcn_bwd_reg_kernel<Q, ZN>: what the forward and the backward both ask of the dims: hid_dim 64,
+// 11 node-feature tiles (dn 161..176), float4 rows in both feature tables, lin_event with Q = 11..14 K steps, and
+// the packs their shared front (gcn_front) streams in that shape: lin_event's K steps and event_gcn's first layer.
+// Each side adds the packs only it streams, at its launch below.
+static bool gcn_reg_dims(const EncW &P) {
     const int nqe = r16(P.kev) / 16;
     return P.h == HID && r16(P.dn) == 176 && P.dn % 4 == 0 && P.de % 4 == 0 && nqe >= 11 && nqe <= 14 &&
-           P.g1.nt == 4 && P.g1.nq == 11 && w->T.g2T.nt == 4 && w->T.g1T.nt == 11 && w->T.g1T.nq == 4 &&
-           w->T.evT.nt == 11 && w->T.evT.nq == 11 && P.ev.nq == nqe;
+           P.g1.nt == 4 && P.g1.nq == 11 && P.ev.nq == nqe;
+}
+// The instance table: f(Q, ZN) with the two as integral-constant types, Q = lin_event's K steps (gcn_reg_dims holds)
+template <class F>
+static void gcn_reg_pick(const EncW &P, int node_zero, F f) {
+    const int nqe = r16(P.kev) / 16;
+    auto q = [&](auto Q) { node_zero ? f(Q, std::true_type{}) : f(Q, std::false_type{}); };
+    if (nqe == 11) q(std::integral_constant<int, 11>{});
+    else if (nqe == 12) q(std::integral_constant<int, 12>{});
+    else if (nqe == 13) q(std::integral_constant<int, 13>{});
+    else q(std::integral_constant<int, 14>{});
 }
 
-// the event_gcn backward launch of tm_encoder_bwd / tm_encoder_pool_bwd: io->dF down to lin_event and the time encoder
-static int launch_gcn_bwd(const tm_weights *w, int64_t n_walks, const float *n_feat, const float *e_feat,
-                          const int32_t *node6, const int32_t *eid3, const float *ts3, const float *cnt,
-                          const tm_encoder_grad_io *io, hipStream_t s) {
+// the register-resident event_gcn training forward (gcn_fwd_reg_kernel) for the dims it has an instance for:
+// 8 % faster per training step than the LDS-tiled gcn_kernel / gcn_bwd_kernel (round 5, tools/train_flags_ab.sh)
+bool tmk::launch_gcn_fwd_reg(const EncW &P, int node_zero, int64_t n_rows, const float *n_feat, const float *e_feat,
+                             const int32_t *node6, const int32_t *eid3, const float *ts3, const float *cnt, float *F,
+                             hipStream_t s) {
+    // the forward alone goes on through MLP.2's pack (g2), and asks lin_event's output tiles of the pack itself
+    // (the backward takes them from r16(dn) == 176, which the pack's builder derives them from)
+    if (!(gcn_reg_dims(P) && P.ev.nt == 11 && P.g2.nt == 4 && P.g2.nq == 4)) return false;
+    const unsigned blocks = (unsigned)((n_rows + 63) / 64);
+    gcn_reg_pick(P, node_zero, [&](auto Q, auto ZN) {
+        gcn_fwd_reg_kernel<decltype(Q)::value, decltype(ZN)::value><<<dim3(blocks), 256, 0, s>>>(
+            P, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, F);
+    });
+    return true;
+}
+
+// One encoder backward: the arguments tm_encoder_bwd and tm_encoder_pool_bwd share, and what the pooled one adds.
+struct EncBwd {
+    const char *who;
+    const tm_weights *w;
+    const float *n_feat, *e_feat;
+    int32_t n_groups, B, W;
+    const int32_t *node6, *eid3;
+    const float *ts3;
+    const int32_t *cat;
+    const double *cut;
+    const float *cnt;
+    const uint8_t *drop;   // keep-masks, nullable
+    float dscale;
+    const void *workspace;   // as the matching training forward left it: F and the groups' std are read
+    const tm_encoder_grad_io *io;
+    void *stream;
+    // the upstream gradient: d_imp [n_walks]; pooled d_emb, one row per event ld_up floats apart of which the
+    // leading h columns are read
+    const float *up;
+    int64_t ld_up = 0;
+    // pooled (the backward of tm_encoder_pool_train_fwd): head_bwd_kernel's POOL instance, the walks weighted by wgt
+    bool pool = false;
+    const float *wgt = nullptr;
+};
+
+// validate, carve the workspace, head_bwd_kernel<16[, POOL]> (d upstream -> io->dF), then the event_gcn backward
+// (io->dF down to lin_event and the time encoder): register-resident or LDS-tiled
+static int encoder_backward(const EncBwd &c) {
+    if (!c.w || !c.io || c.n_groups < 0 || c.B < 0 || c.W < 0) return refuse(TM_E_ARG, c.who, "bad arguments");
+    const int64_t n_walks = (int64_t)c.n_groups * c.B * c.W;
+    if (n_walks == 0) return TM_OK;
+    const tm_weights *w = c.w;
+    const tm_encoder_grad_io *io = c.io;
     const EncW &P = w->P;
+    // (the pooled call tests its leading dimension before the pointers)
+    if (c.pool && c.ld_up < P.h) return refuse(TM_E_ARG, c.who, "ld_demb below hid_dim");
+    if (!c.n_feat || !c.e_feat || !c.node6 || !c.eid3 || !c.ts3 || !c.cat || !c.cut || !c.cnt || !c.workspace ||
+        !c.up || (c.pool && !c.wgt))
+        return refuse(TM_E_ARG, c.who, "NULL pointer");
+    // dY2 .. dt are both calls'; the scoring MLP's six buffers the plain call's alone (the POOL instance touches
+    // neither them nor imp, which may be NULL in both)
+    if ((!c.pool && (!io->dlogit || !io->M2 || !io->dM2 || !io->M1d || !io->dM1 || !io->X)) || !io->dY2 ||
+        !io->H1d || !io->dH1 || !io->O || !io->dP || !io->dQ || !io->dF || !io->ev || !io->AB || !io->H || !io->dZ ||
+        !io->dlev || !io->g || !io->dt)
+        return refuse(TM_E_ARG, c.who, "NULL output buffer");
+    if (!w->tbuf) return refuse(TM_E_ARG, c.who, "weights have no transposed packs");
+    if (!enc_bwd_fits(P)) return refuse(TM_E_UNSUPPORTED, c.who, "LDS budget exceeded");
+    hipStream_t s = S_(c.stream);
+    const EncWs ws = enc_ws(w, n_walks, const_cast<void *>(c.workspace));   // read only
+    const dim3 hgrid((unsigned)((n_walks + 15) / 16));
+    hipEvent_t pe = prof_begin(s);
+    HeadBwdOut ho{io->imp, io->dlogit, io->M2, io->dM2, io->M1d, io->dM1, io->X, io->dY2, io->H1d, io->dH1, io->O,
+                  io->dP,  io->dQ,     io->dF};
+    if (c.pool) {   // its own, smaller tile (neither [TR][LDM] one), and none of the plain call's seven buffers
+        ho.imp = ho.dlogit = ho.M2 = ho.dM2 = ho.M1d = ho.dM1 = ho.X = nullptr;
+        head_bwd_kernel<16, true><<<hgrid, 256, sizeof(float) * head_pool_bwd_lds_floats(P.h, 16), s>>>(
+            P, w->T, n_walks, (int64_t)c.B * c.W, c.W, ws.F, c.ts3, c.cut, c.cat, ws.stdv, c.drop, c.dscale, nullptr, ho,
+            c.wgt, c.up, c.ld_up);
+    } else {
+        head_bwd_kernel<16><<<hgrid, 256, sizeof(float) * head_bwd_lds_floats(P.h, P.hm, 16), s>>>(
+            P, w->T, n_walks, (int64_t)c.B * c.W, c.W, ws.F, c.ts3, c.cut, c.cat, ws.stdv, c.drop, c.dscale, c.up, ho);
+    }
+    TM_CHECK_LAUNCH();
+    prof_end(c.pool ? "head_pool_bwd_kernel" : "head_bwd_kernel", s, pe);
     const int64_t n_rows = n_walks * 3;
     GcnBwdOut go{io->ev, io->AB, io->H, io->dZ, io->dlev, io->g, io->dt};
-    hipEvent_t pe = prof_begin(s);
-    const int nqe = r16(P.kev) / 16;
-    // register-resident instance: hid_dim 64, 11 node-feature tiles (dn 161..176, a multiple of 4), lin_event
-    // with 11..14 K steps; the LDS-tiled kernel otherwise
-    const bool reg = gcn_bwd_uses_reg(w);
-    if (reg) {
+    pe = prof_begin(s);
+    // the register-resident backward alone streams the transposed packs: dZ through MLP.2^T (g2T), d lin_event
+    // through MLP.0^T (g1T), the time features' gradient through lin_event's time columns^T (evT)
+    const EncWT &T = w->T;
+    if (gcn_reg_dims(P) && T.g2T.nt == 4 && T.g1T.nt == 11 && T.g1T.nq == 4 && T.evT.nt == 11 && T.evT.nq == 11) {
         const unsigned blocks = (unsigned)((n_rows + 63) / 64);
-#define TM_BWD_REG(Q)                                                                                              \
-        (w->node_zero ? gcn_bwd_reg_kernel<Q, true><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
-                                                                                 eid3, ts3, cnt, io->dF, go)          \
-                      : gcn_bwd_reg_kernel<Q, false><<<dim3(blocks), 256, 0, s>>>(P, w->T, n_rows, n_feat, e_feat, node6, \
-                                                                                  eid3, ts3, cnt, io->dF, go))
-        if (nqe == 11) TM_BWD_REG(11);
-        else if (nqe == 12) TM_BWD_REG(12);
-        else if (nqe == 13) TM_BWD_REG(13);
-        else TM_BWD_REG(14);
-#undef TM_BWD_REG
-    } else if (w->node_zero) {
-        gcn_bwd_kernel<true><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, gcn_bwd_lds(P), s>>>(
-            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
+        gcn_reg_pick(P, w->node_zero, [&](auto Q, auto ZN) {
+            gcn_bwd_reg_kernel<decltype(Q)::value, decltype(ZN)::value><<<dim3(blocks), 256, 0, s>>>(
+                P, w->T, n_rows, c.n_feat, c.e_feat, c.node6, c.eid3, c.ts3, c.cnt, io->dF, go);
+        });
     } else {
-        gcn_bwd_kernel<false><<<dim3((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS)), 256, gcn_bwd_lds(P), s>>>(
-            P, w->T, n_rows, n_feat, e_feat, node6, eid3, ts3, cnt, io->dF, go);
+        const dim3 grid((unsigned)((n_rows + TILE_ROWS - 1) / TILE_ROWS));
+        if (w->node_zero)
+            gcn_bwd_kernel<true><<<grid, 256, gcn_bwd_lds(P), s>>>(P, w->T, n_rows, c.n_feat, c.e_feat, c.node6, c.eid3,
+                                                                   c.ts3, c.cnt, io->dF, go);
+        else
+            gcn_bwd_kernel<false><<<grid, 256, gcn_bwd_lds(P), s>>>(P, w->T, n_rows, c.n_feat, c.e_feat, c.node6, c.eid3,
+                                                                    c.ts3, c.cnt, io->dF, go);
     }
     TM_CHECK_LAUNCH();
     prof_end("gcn_bwd_kernel", s, pe);
@@ -1793,30 +1877,8 @@ extern "C" int tm_encoder_bwd(const tm_weights *w, const float *n_feat, const fl
                               const int32_t *cat, const double *cut, const float *cnt, const uint8_t *drop,
                               float drop_scale, const void *workspace, const float *d_imp, const tm_encoder_grad_io *io,
                               void *stream) {
-    if (!w || !io || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_bwd: bad arguments");
-    const int64_t n_walks = (int64_t)n_groups * B * W;
-    if (n_walks == 0) return TM_OK;
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !workspace || !d_imp)
-        return fail(TM_E_ARG, "tm_encoder_bwd: NULL pointer");
-    if (!io->dlogit || !io->M2 || !io->dM2 || !io->M1d || !io->dM1 || !io->X || !io->dY2 || !io->H1d || !io->dH1 ||
-        !io->O || !io->dP || !io->dQ || !io->dF || !io->ev || !io->AB || !io->H || !io->dZ || !io->dlev || !io->g ||
-        !io->dt)
-        return fail(TM_E_ARG, "tm_encoder_bwd: NULL output buffer");
-    if (!w->tbuf) return fail(TM_E_ARG, "tm_encoder_bwd: weights have no transposed packs");
-    const EncW &P = w->P;
-    const int tr = head_bwd_tr(P);
-    const size_t lh = sizeof(float) * head_bwd_lds_floats(P.h, P.hm, tr), lg = gcn_bwd_lds(P);
-    if (P.h % 16 || !tr || lg > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_encoder_bwd: LDS budget exceeded");
-    hipStream_t s = S_(stream);
-    const EncWs ws = enc_ws(w, n_walks, const_cast<void *>(workspace));   // read only
-    HeadBwdOut ho{io->imp, io->dlogit, io->M2, io->dM2, io->M1d, io->dM1, io->X, io->dY2, io->H1d, io->dH1, io->O,
-                  io->dP,  io->dQ,     io->dF};
-    hipEvent_t pe = prof_begin(s);
-    head_bwd_kernel<16><<<dim3((unsigned)((n_walks + 15) / 16)), 256, lh, s>>>(
-        P, w->T, n_walks, (int64_t)B * W, W, ws.F, ts3, cut, cat, ws.stdv, drop, drop_scale, d_imp, ho);
-    TM_CHECK_LAUNCH();
-    prof_end("head_bwd_kernel", s, pe);
-    return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
+    return encoder_backward({"tm_encoder_bwd", w, n_feat, e_feat, n_groups, B, W, node6, eid3, ts3, cat, cut, cnt, drop,
+                             drop_scale, workspace, io, stream, d_imp});
 }
 
 // Backward of tm_encoder_pool_train_fwd given d_emb = dL/d out (rows ld_demb floats apart; only the leading h
@@ -1826,53 +1888,8 @@ extern "C" int tm_encoder_pool_bwd(const tm_weights *w, const float *n_feat, con
                                    const int32_t *cat, const double *cut, const float *cnt, const float *wgt,
                                    const uint8_t *drop, float drop_scale, const void *workspace, const float *d_emb,
                                    int64_t ld_demb, const tm_encoder_grad_io *io, void *stream) {
-    if (!w || !io || n_groups < 0 || B < 0 || W < 0) return fail(TM_E_ARG, "tm_encoder_pool_bwd: bad arguments");
-    const int64_t n_walks = (int64_t)n_groups * B * W;
-    if (n_walks == 0) return TM_OK;
-    const EncW &P = w->P;
-    if (ld_demb < P.h) return fail(TM_E_ARG, "tm_encoder_pool_bwd: ld_demb below hid_dim");
-    if (!n_feat || !e_feat || !node6 || !eid3 || !ts3 || !cat || !cut || !cnt || !wgt || !workspace || !d_emb)
-        return fail(TM_E_ARG, "tm_encoder_pool_bwd: NULL pointer");
-    if (!io->dY2 || !io->H1d || !io->dH1 || !io->O || !io->dP || !io->dQ || !io->dF || !io->ev || !io->AB || !io->H ||
-        !io->dZ || !io->dlev || !io->g || !io->dt)
-        return fail(TM_E_ARG, "tm_encoder_pool_bwd: NULL output buffer");
-    if (!w->tbuf) return fail(TM_E_ARG, "tm_encoder_pool_bwd: weights have no transposed packs");
-    const size_t lh = sizeof(float) * head_pool_bwd_lds_floats(P.h, 16);
-    if (P.h % 16 || !head_bwd_tr(P) || gcn_bwd_lds(P) > 160 * 1024)
-        return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_bwd: LDS budget exceeded");
-    hipStream_t s = S_(stream);
-    const EncWs ws = enc_ws(w, n_walks, const_cast<void *>(workspace));   // read only
-    HeadBwdOut ho{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, io->dY2, io->H1d, io->dH1, io->O,
-                  io->dP,  io->dQ,  io->dF};
-    hipEvent_t pe = prof_begin(s);
-    head_bwd_kernel<16, true><<<dim3((unsigned)((n_walks + 15) / 16)), 256, lh, s>>>(
-        P, w->T, n_walks, (int64_t)B * W, W, ws.F, ts3, cut, cat, ws.stdv, drop, drop_scale, nullptr, ho, wgt, d_emb, ld_demb);
-    TM_CHECK_LAUNCH();
-    prof_end("head_pool_bwd_kernel", s, pe);
-    return launch_gcn_bwd(w, n_walks, n_feat, e_feat, node6, eid3, ts3, cnt, io, s);
-}
-
-// the register-resident event_gcn training forward (gcn_fwd_reg_kernel) for the dims it has an instance for:
-// 8 % faster per training step than the LDS-tiled gcn_kernel / gcn_bwd_kernel (round 5, tools/train_flags_ab.sh)
-bool tmk::launch_gcn_fwd_reg(const EncW &P, int node_zero, int64_t n_rows, const float *n_feat, const float *e_feat,
-                             const int32_t *node6, const int32_t *eid3, const float *ts3, const float *cnt, float *F,
-                             hipStream_t s) {
-    const int nqe = r16(P.kev) / 16;
-    if (!(P.h == HID && r16(P.dn) == 176 && P.dn % 4 == 0 && P.de % 4 == 0 && nqe >= 11 && nqe <= 14 &&
-          P.ev.nt == 11 && P.ev.nq == nqe && P.g1.nt == 4 && P.g1.nq == 11 && P.g2.nt == 4 && P.g2.nq == 4))
-        return false;
-    const unsigned blocks = (unsigned)((n_rows + 63) / 64);
-#define TM_FWD_REG(Q)                                                                                              \
-    (node_zero ? gcn_fwd_reg_kernel<Q, true><<<dim3(blocks), 256, 0, s>>>(P, n_rows, n_feat, e_feat, node6, eid3, ts3, \
-                                                                          cnt, F)                                    \
-               : gcn_fwd_reg_kernel<Q, false><<<dim3(blocks), 256, 0, s>>>(P, n_rows, n_feat, e_feat, node6, eid3, ts3, \
-                                                                           cnt, F))
-    if (nqe == 11) TM_FWD_REG(11);
-    else if (nqe == 12) TM_FWD_REG(12);
-    else if (nqe == 13) TM_FWD_REG(13);
-    else TM_FWD_REG(14);
-#undef TM_FWD_REG
-    return true;
+    return encoder_backward({"tm_encoder_pool_bwd", w, n_feat, e_feat, n_groups, B, W, node6, eid3, ts3, cat, cut, cnt,
+                             drop, drop_scale, workspace, io, stream, d_emb, ld_demb, true, wgt});
 }
 
 // Shared driver of the weight-gradient launches: jobs (dY, X, rows) and targets (dW, db, job range).
@@ -1951,22 +1968,25 @@ extern "C" int tm_wgrad(const tm_wgrad_job *jobs, int32_t n_jobs, const tm_wgrad
     return run_wgrad(jobs, n_jobs, targets, n_targets, S_(stream), "tm_wgrad");
 }
 
-extern "C" int tm_encoder_wgrad(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W,
-                                const tm_encoder_grad_io *io, const void *workspace, float *const *grads,
-                                void *stream) {
-    if (!w || !io || !workspace || !grads || n_groups < 0 || B < 0 || W < 0)
-        return fail(TM_E_ARG, "tm_encoder_wgrad: bad arguments");
-    for (int i = 0; i < TM_N_ENC_GRADS; ++i)
-        if (!grads[i]) return fail(TM_E_ARG, "tm_encoder_wgrad: NULL gradient " + std::to_string(i));
+// The encoder's weight-gradient jobs and targets, once: tm_encoder_wgrad's 12 jobs for 11 targets, and with `pool`
+// tm_encoder_pool_wgrad's -- the same without the scoring MLP's three (MLP.0 / .3 / .5 take no part in the pooled
+// encoder), so the time encoder's job moves up to index 8 and TM_N_POOL_GRADS gradients are read.
+static int encoder_wgrad(const char *who, bool pool, const tm_weights *w, int32_t n_groups, int32_t B, int32_t W,
+                         const tm_encoder_grad_io *io, const void *workspace, float *const *grads, void *stream) {
+    if (!w || !io || !workspace || !grads || n_groups < 0 || B < 0 || W < 0) return refuse(TM_E_ARG, who, "bad arguments");
+    const int ngrad = pool ? TM_N_POOL_GRADS : TM_N_ENC_GRADS;
+    for (int i = 0; i < ngrad; ++i)
+        if (!grads[i]) return fail(TM_E_ARG, std::string(who) + ": NULL gradient " + std::to_string(i));
     const int64_t n64 = (int64_t)n_groups * B * W;
-    if (n64 * 3 * 2 > INT32_MAX) return fail(TM_E_UNSUPPORTED, "tm_encoder_wgrad: too many walks per call");
+    if (n64 * 3 * 2 > INT32_MAX) return refuse(TM_E_UNSUPPORTED, who, "too many walks per call");
     const int n = (int)n64, R = 3 * n, h = w->h, h2 = 2 * h, hm = w->P.hm;
     const int dn = w->dn, kev = w->P.kev, KE = r16(kev), DN = r16(dn), KM = r16(hm);
     const float *F = reinterpret_cast<const float *>(workspace);
     // zero node features (gcn_bwd_kernel<true>): one row pair per position for MLP.0 / MLP.2, the branch sums
     const bool zn = w->node_zero;   // both event_gcn backward kernels have the zero-node form
     const tm_wgrad_job zn0{io->dZ, io->AB, 2 * h, 2 * DN, h, dn, R}, zn2{io->dZ + h, io->H, 2 * h, 2 * h, h, h, R};
-    const tm_wgrad_job jobs[] = {
+    const tm_wgrad_job time_enc{io->g, io->dt, DN, 1, dn, 1, R};   // freq (x = dt), phase (ones)
+    tm_wgrad_job jobs[] = {
         {io->dlev, io->ev, DN, KE, dn, kev, R},            // lin_event
         zn ? zn0 : tm_wgrad_job{io->dZ, io->AB, h, DN, h, dn, 2 * R},   // event_conv.MLP.0
         zn ? zn2 : tm_wgrad_job{io->dF, io->H, h, h, h, h, 2 * R},      // event_conv.MLP.2
@@ -1974,61 +1994,68 @@ extern "C" int tm_encoder_wgrad(const tm_weights *w, int32_t n_groups, int32_t B
         {io->dQ, F, h2, 3 * h2, h2, h2, n},                // attention.W2, position 0
         {io->dQ + (int64_t)n * h2, F + h2, h2, 3 * h2, h2, h2, n},   // position 1
         {io->dH1, io->O, h, h2, h, h2, n},                 // attention.MLP.0
-        {io->dY2, io->H1d, h, h, h, h, n},                 // attention.MLP.3
+        {io->dY2, io->H1d, h, h, h, h, n},                 // attention.MLP.3 (pooled, its bias: sum_w wgt_w d_emb)
         {io->dM1, io->X, KM, KM, hm, hm, n},               // MLP.0
         {io->dM2, io->M1d, h, KM, h, hm, n},               // MLP.3
         {io->dlogit, io->M2, 1, h, 1, h, n},               // MLP.5
-        {io->g, io->dt, DN, 1, dn, 1, R},                  // time encoder: freq (x = dt), phase (ones)
+        time_enc,
     };
-    const tm_wgrad_target tgts[] = {{grads[0], grads[1], 0, 1},   {grads[2], grads[3], 1, 1},
-                                    {grads[4], grads[5], 2, 1},   {grads[6], grads[7], 3, 1},
-                                    {grads[8], grads[9], 4, 2},   {grads[10], grads[11], 6, 1},
-                                    {grads[12], grads[13], 7, 1}, {grads[14], grads[15], 8, 1},
-                                    {grads[16], grads[17], 9, 1}, {grads[18], grads[19], 10, 1},
-                                    {grads[20], grads[21], 11, 1}};
-    return run_wgrad(jobs, (int)(sizeof(jobs) / sizeof(jobs[0])), tgts, (int)(sizeof(tgts) / sizeof(tgts[0])),
-                     S_(stream), "tm_encoder_wgrad");
+    int njob = (int)(sizeof(jobs) / sizeof(jobs[0]));
+    if (pool) jobs[8] = time_enc, njob = 9;
+    // target t takes grads[2t], grads[2t + 1] and the next job; attention.W2's takes both positions
+    tm_wgrad_target tgts[TM_N_ENC_GRADS / 2];
+    int ntgt = 0;
+    for (int j = 0; j < njob; ++ntgt) {
+        const int nj = j == 4 ? 2 : 1;
+        tgts[ntgt] = {grads[2 * ntgt], grads[2 * ntgt + 1], j, nj};
+        j += nj;
+    }
+    return run_wgrad(jobs, njob, tgts, ntgt, S_(stream), who);
 }
 
-// tm_encoder_wgrad without the scoring MLP (MLP.0 / .3 / .5 take no part in the pooled encoder): the same jobs
+extern "C" int tm_encoder_wgrad(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W,
+                                const tm_encoder_grad_io *io, const void *workspace, float *const *grads,
+                                void *stream) {
+    return encoder_wgrad("tm_encoder_wgrad", false, w, n_groups, B, W, io, workspace, grads, stream);
+}
+
+// tm_encoder_wgrad without the scoring MLP
 extern "C" int tm_encoder_pool_wgrad(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W,
                                      const tm_encoder_grad_io *io, const void *workspace, float *const *grads,
                                      void *stream) {
-    if (!w || !io || !workspace || !grads || n_groups < 0 || B < 0 || W < 0)
-        return fail(TM_E_ARG, "tm_encoder_pool_wgrad: bad arguments");
-    for (int i = 0; i < TM_N_POOL_GRADS; ++i)
-        if (!grads[i]) return fail(TM_E_ARG, "tm_encoder_pool_wgrad: NULL gradient " + std::to_string(i));
-    const int64_t n64 = (int64_t)n_groups * B * W;
-    if (n64 * 3 * 2 > INT32_MAX) return fail(TM_E_UNSUPPORTED, "tm_encoder_pool_wgrad: too many walks per call");
-    const int n = (int)n64, R = 3 * n, h = w->h, h2 = 2 * h;
-    const int dn = w->dn, kev = w->P.kev, KE = r16(kev), DN = r16(dn);
-    const float *F = reinterpret_cast<const float *>(workspace);
-    const bool zn = w->node_zero;   // the zero-node row-pair form of tm_encoder_wgrad
-    const tm_wgrad_job zn0{io->dZ, io->AB, 2 * h, 2 * DN, h, dn, R}, zn2{io->dZ + h, io->H, 2 * h, 2 * h, h, h, R};
-    const tm_wgrad_job jobs[] = {
-        {io->dlev, io->ev, DN, KE, dn, kev, R},            // lin_event
-        zn ? zn0 : tm_wgrad_job{io->dZ, io->AB, h, DN, h, dn, 2 * R},   // event_conv.MLP.0
-        zn ? zn2 : tm_wgrad_job{io->dF, io->H, h, h, h, h, 2 * R},      // event_conv.MLP.2
-        {io->dP, F + 2 * h2, h2, 3 * h2, h2, h2, n},       // attention.W1 (x = F[:, 2])
-        {io->dQ, F, h2, 3 * h2, h2, h2, n},                // attention.W2, position 0
-        {io->dQ + (int64_t)n * h2, F + h2, h2, 3 * h2, h2, h2, n},   // position 1
-        {io->dH1, io->O, h, h2, h, h2, n},                 // attention.MLP.0
-        {io->dY2, io->H1d, h, h, h, h, n},                 // attention.MLP.3 (bias: sum_w wgt_w d_emb)
-        {io->g, io->dt, DN, 1, dn, 1, R},                  // time encoder: freq (x = dt), phase (ones)
-    };
-    const tm_wgrad_target tgts[] = {{grads[0], grads[1], 0, 1},   {grads[2], grads[3], 1, 1},
-                                    {grads[4], grads[5], 2, 1},   {grads[6], grads[7], 3, 1},
-                                    {grads[8], grads[9], 4, 2},   {grads[10], grads[11], 6, 1},
-                                    {grads[12], grads[13], 7, 1}, {grads[14], grads[15], 8, 1}};
-    return run_wgrad(jobs, (int)(sizeof(jobs) / sizeof(jobs[0])), tgts, (int)(sizeof(tgts) / sizeof(tgts[0])),
-                     S_(stream), "tm_encoder_pool_wgrad");
+    return encoder_wgrad("tm_encoder_pool_wgrad", true, w, n_groups, B, W, io, workspace, grads, stream);
 }
 
 static int explain_train_fwd(const tm_weights *w, const float *e_feat, int32_t n_groups, int32_t B, int32_t W,
                              int32_t N, const int32_t *eid3, const float *ts3, const float *imp, const int32_t *sub1_eid,
                              const int32_t *sub2_eid, const uint8_t *keep1, const uint8_t *keep2, float scale1,
                              float scale2, const tm_explain_grad_io *io, float *p1, float *p2, const int32_t *sub1_node,
-                             const int32_t *sub2_node, float *pad1, float *pad2, void *stream);
+                             const int32_t *sub2_node, float *pad1, float *pad2, void *stream) {
+    if (!w || !io || n_groups < 0 || B < 0 || W <= 0 || N <= 0) return fail(TM_E_ARG, "tm_explain_train_fwd: bad arguments");
+    const int64_t rows = (int64_t)n_groups * B;
+    if (rows == 0) return TM_OK;
+    if (!e_feat || !eid3 || !ts3 || !imp || !sub1_eid || !sub2_eid || !p1 || !p2 || !io->X || !io->G1 || !io->G2 ||
+        !io->z || !io->gate || !io->t)
+        return fail(TM_E_ARG, "tm_explain_train_fwd: NULL pointer");
+    const int hb = expl_hbits(W);
+    if (hb > 12) return fail(TM_E_UNSUPPORTED, "tm_explain_train_fwd: too many walks per event");
+    const EncW &P = w->P;
+    hipStream_t s = S_(stream);
+    const int64_t R = rows * 3 * W;
+    ExplIO o{io->X, io->G1, io->G2, io->z, io->gate, io->d_gate, io->dz, io->dG2, io->dG1, io->g, io->t};
+    if (gate_fwd_lds(P) > LDS_BUDGET) return fail(TM_E_UNSUPPORTED, "tm_explain_train_fwd: LDS budget exceeded");
+    hipEvent_t pe = prof_begin(s);
+    gate_train_fwd_kernel<<<dim3((unsigned)((R + TILE_ROWS - 1) / TILE_ROWS)), 256, gate_fwd_lds(P), s>>>(
+        P, R, e_feat, eid3, ts3, keep1, keep2, scale1, scale2, o);
+    TM_CHECK_LAUNCH();
+    prof_end("gate_train_fwd_kernel", s, pe);
+    pe = prof_begin(s);
+    explain_train_kernel<<<dim3((unsigned)rows), 256, 2 * sizeof(int32_t) * (1u << hb), s>>>(
+        W, N, hb, eid3, imp, io->gate, sub1_eid, sub2_eid, p1, p2, sub1_node, sub2_node, pad1, pad2);
+    TM_CHECK_LAUNCH();
+    prof_end("explain_train_kernel", s, pe);
+    return TM_OK;
+}
 
 extern "C" int tm_explain_train_fwd(const tm_weights *w, const float *e_feat, int32_t n_groups, int32_t B, int32_t W,
                                     int32_t N, const int32_t *eid3, const float *ts3, const float *imp,
@@ -2049,38 +2076,6 @@ extern "C" int tm_explain_train_fwd_pad(const tm_weights *w, const float *e_feat
     if (!sub1_node || !sub2_node || !pad1 || !pad2) return fail(TM_E_ARG, "tm_explain_train_fwd_pad: NULL pointer");
     return explain_train_fwd(w, e_feat, n_groups, B, W, N, eid3, ts3, imp, sub1_eid, sub2_eid, keep1, keep2, scale1,
                              scale2, io, p1, p2, sub1_node, sub2_node, pad1, pad2, stream);
-}
-
-static int explain_train_fwd(const tm_weights *w, const float *e_feat, int32_t n_groups, int32_t B, int32_t W,
-                             int32_t N, const int32_t *eid3, const float *ts3, const float *imp, const int32_t *sub1_eid,
-                             const int32_t *sub2_eid, const uint8_t *keep1, const uint8_t *keep2, float scale1,
-                             float scale2, const tm_explain_grad_io *io, float *p1, float *p2, const int32_t *sub1_node,
-                             const int32_t *sub2_node, float *pad1, float *pad2, void *stream) {
-    if (!w || !io || n_groups < 0 || B < 0 || W <= 0 || N <= 0) return fail(TM_E_ARG, "tm_explain_train_fwd: bad arguments");
-    const int64_t rows = (int64_t)n_groups * B;
-    if (rows == 0) return TM_OK;
-    if (!e_feat || !eid3 || !ts3 || !imp || !sub1_eid || !sub2_eid || !p1 || !p2 || !io->X || !io->G1 || !io->G2 ||
-        !io->z || !io->gate || !io->t)
-        return fail(TM_E_ARG, "tm_explain_train_fwd: NULL pointer");
-    const int hb = expl_hbits(W);
-    if (hb > 12) return fail(TM_E_UNSUPPORTED, "tm_explain_train_fwd: too many walks per event");
-    const EncW &P = w->P;
-    hipStream_t s = S_(stream);
-    const int64_t R = rows * 3 * W;
-    ExplIO o{io->X, io->G1, io->G2, io->z, io->gate, io->d_gate, io->dz, io->dG2, io->dG1, io->g, io->t};
-    const size_t lds = sizeof(float) * (TILE_ROWS * (r16(P.kdep) + 8) + TILE_ROWS * (r16(P.h) + 8) + TILE_ROWS * (r16(P.h / 2) + 8));
-    if (lds > 160 * 1024) return fail(TM_E_UNSUPPORTED, "tm_explain_train_fwd: LDS budget exceeded");
-    hipEvent_t pe = prof_begin(s);
-    gate_train_fwd_kernel<<<dim3((unsigned)((R + TILE_ROWS - 1) / TILE_ROWS)), 256, lds, s>>>(
-        P, R, e_feat, eid3, ts3, keep1, keep2, scale1, scale2, o);
-    TM_CHECK_LAUNCH();
-    prof_end("gate_train_fwd_kernel", s, pe);
-    pe = prof_begin(s);
-    explain_train_kernel<<<dim3((unsigned)rows), 256, 2 * sizeof(int32_t) * (1u << hb), s>>>(
-        W, N, hb, eid3, imp, io->gate, sub1_eid, sub2_eid, p1, p2, sub1_node, sub2_node, pad1, pad2);
-    TM_CHECK_LAUNCH();
-    prof_end("explain_train_kernel", s, pe);
-    return TM_OK;
 }
 
 extern "C" int tm_explain_train_bwd(const tm_weights *w, int32_t n_groups, int32_t B, int32_t W, int32_t N,
@@ -2111,9 +2106,8 @@ extern "C" int tm_explain_train_bwd(const tm_weights *w, int32_t n_groups, int32
         TM_CHECK_LAUNCH();
         prof_end("explain_train_bwd_kernel", s, pe);
         if (P.dep) {   // no gate without dependency-aware sampling: d imp is the whole backward
-            const size_t lds = sizeof(float) * (TILE_ROWS * (r16(P.h) + 8) + TILE_ROWS * (r16(P.h / 2) + 8));
             pe = prof_begin(s);
-            gate_train_bwd_kernel<<<dim3((unsigned)((R64 + TILE_ROWS - 1) / TILE_ROWS)), 256, lds, s>>>(
+            gate_train_bwd_kernel<<<dim3((unsigned)((R64 + TILE_ROWS - 1) / TILE_ROWS)), 256, gate_bwd_lds(P), s>>>(
                 P, w->T, R64, keep1, keep2, scale1, scale2, o);
             TM_CHECK_LAUNCH();
             prof_end("gate_train_bwd_kernel", s, pe);

@@ -107,6 +107,10 @@ class event_gcn(nn.Module):  # noqa: N801  (reference name, kept for state_dict 
         return self.MLP(src_features + self.relu(tgt_features + event))
 
 
+def _r16(x):   # x rounded up to a multiple of 16, the kernels' tile (r16 in csrc/encoder_common.h)
+    return -(-x // 16) * 16
+
+
 def _to(x, device, dtype):
     if isinstance(x, torch.Tensor):
         if x.dtype == dtype and x.device == device:
@@ -429,7 +433,7 @@ class TempME(nn.Module):
 
     def _hid_packed(self):
         """The hidden width the kernels run at: hid_dim rounded up to a multiple of 16 (their tile)."""
-        return -(-self.hid_dim // 16) * 16
+        return _r16(self.hid_dim)
 
     def _pad_maps(self, dev):
         """Index maps of the zero-padding (_pad_hidden), cached per device: hm = the h hidden units, gm = the
@@ -497,7 +501,7 @@ class TempME(nn.Module):
             return drop
         m = self._pad_maps(drop.device)
         h, H = self.hid_dim, self._hid_packed()
-        ncol = -(-(2 + H + m["M2"]) // 16) * 16
+        ncol = _r16(2 + H + m["M2"])
         src = torch.zeros(ncol, dtype=torch.long, device=drop.device)
         src[:2] = torch.arange(2, device=drop.device)
         src[2 + m["hm"]] = 2 + m["hm"]
@@ -611,7 +615,7 @@ class TempME(nn.Module):
     def dropout_cols(self):
         """Columns of a dropout keep-mask row (include/tempme.h, tm_encoder_train_fwd): alpha 2, attention.MLP
         hidden h, MLP hidden mlp_dim, rounded up to 16 -- 144 for the default constructor."""
-        return -(-(2 + self.hid_dim + self.mlp_dim) // 16) * 16
+        return _r16(2 + self.hid_dim + self.mlp_dim)
 
     def dropout_masks(self, n_walks):
         """Keep-masks of the three dropouts TempME.forward applies in training (explainer_new.py:839 alpha,
@@ -658,27 +662,37 @@ class TempME(nn.Module):
         node6, eid3, ts3, cat, cut, cnt, G, B, W = args
         dev = self._dev()
         nt, et = self.feature_tables()
-        n = G * B * W
-        R = 3 * n
         drop = self._drop_packed(drop)
-        de, dn, h = self.edge_dim, self.node_dim, self._hid_packed()   # the packed (padded) widths
-        kev = de + 3 + dn
-        KE, DN, KM = -(-kev // 16) * 16, -(-dn // 16) * 16, -(-(h + 12 if self.if_cat else h) // 16) * 16
-        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-        b = dict(imp=None, dlogit=e(n), M2=e(n, h), dM2=e(n, h), M1d=e(n, KM), dM1=e(n, KM), X=e(n, KM), dY2=e(n, h),
-                 H1d=e(n, h), dH1=e(n, h), O=e(n, 2 * h), dP=e(n, 2 * h), dQ=e(2, n, 2 * h), dF=e(n, 3, 2 * h),
-                 ev=e(R, KE), AB=e(R, 2, DN), H=e(R, 2, h), dZ=e(R, 2, h), dlev=e(R, DN), g=e(R, DN), dt=e(R))
-        io = L.EncoderGradIO(*[None if b[k] is None else b[k].data_ptr() for k in L.GRAD_IO_FIELDS])
+        keep, io = self._grad_io(G * B * W)   # keep: the buffers io points at, alive to the end
         d_imp = d_imp.to(dev, torch.float32).contiguous()
         L.check(L.lib().tm_encoder_bwd(self.packed_weights(), L.ptr(nt), L.ptr(et), G, B, W, L.ptr(node6),
                                        L.ptr(eid3), L.ptr(ts3), L.ptr(cat), L.ptr(cut), L.ptr(cnt), L.ptr(drop),
                                        drop_scale, L.ptr(ws), L.ptr(d_imp), L.C.byref(io), L.stream_ptr(dev)),
                 "TempME.forward backward")
-        grads = [e(*s) for s in self._padded_shapes(_ENC_IDX)]
+        return self._wgrad(L.lib().tm_encoder_wgrad, _ENC_IDX, (G, B, W), io, ws, "TempME.forward weight gradients")
+
+    def _grad_io(self, n, pool=False):
+        """tm_encoder_grad_io's buffers (include/tempme.h) for n walks, R = 3 n walk positions, at the packed
+        (padded) widths -> ({field: tensor}, L.EncoderGradIO).  imp stays NULL; pool: so do the scoring MLP's six
+        buffers, which tm_encoder_pool_bwd / _pool_wgrad do not touch."""
+        dev = self._dev()
+        h, R = self._hid_packed(), 3 * n
+        KE, DN, KM = _r16(self.edge_dim + 3 + self.node_dim), _r16(self.node_dim), _r16(h + 12 if self.if_cat else h)
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        b = {} if pool else dict(dlogit=e(n), M2=e(n, h), dM2=e(n, h), M1d=e(n, KM), dM1=e(n, KM), X=e(n, KM))
+        b.update(dY2=e(n, h), H1d=e(n, h), dH1=e(n, h), O=e(n, 2 * h), dP=e(n, 2 * h), dQ=e(2, n, 2 * h),
+                 dF=e(n, 3, 2 * h), ev=e(R, KE), AB=e(R, 2, DN), H=e(R, 2, h), dZ=e(R, 2, h), dlev=e(R, DN), g=e(R, DN),
+                 dt=e(R))
+        return b, L.EncoderGradIO(*[b[k].data_ptr() if k in b else None for k in L.GRAD_IO_FIELDS])
+
+    def _wgrad(self, fn, idx, gbw, io, ws, what):
+        """A backward's tail: fn (tm_encoder_wgrad / tm_encoder_pool_wgrad) into padded buffers for the tm_weights
+        indices idx, read back as the gradients of the module's own parameters."""
+        dev = self._dev()
+        grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in self._padded_shapes(idx)]
         gp = (L.C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
-        L.check(L.lib().tm_encoder_wgrad(self.packed_weights(), G, B, W, L.C.byref(io), L.ptr(ws), gp,
-                                         L.stream_ptr(dev)), "TempME.forward weight gradients")
-        return tuple(self._unpad_grads(grads, _ENC_IDX))
+        L.check(fn(self.packed_weights(), *gbw, L.C.byref(io), L.ptr(ws), gp, L.stream_ptr(dev)), what)
+        return tuple(self._unpad_grads(grads, idx))
 
     def _gate_params(self):
         """edge_dependency_gcn's three Linear pairs and the time encoder (the cached weight list)."""
@@ -728,7 +742,7 @@ class TempME(nn.Module):
     def _expl_io(self, R):
         dev = self._dev()
         h, dn = self._hid_packed(), self.node_dim
-        KD, DN = -(-(self.edge_dim + dn) // 16) * 16, -(-dn // 16) * 16
+        KD, DN = _r16(self.edge_dim + dn), _r16(dn)
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         b = dict(X=e(R, KD), G1=e(R, h), G2=e(R, h // 2), z=e(R), gate=e(R), d_gate=e(R), dz=e(R), dG2=e(R, h // 2),
                  dG1=e(R, h), g=e(R, DN), t=e(R))
@@ -1430,31 +1444,21 @@ class TempME(nn.Module):
         dev = self._dev()
         nt, et = self.feature_tables()
         w = self.packed_weights()
-        n = G * B * W
-        R = 3 * n
         drop = self._drop_packed(drop)
-        de, dn, hh, h = self.edge_dim, self.node_dim, self.hid_dim, self._hid_packed()   # h: the packed (padded) width
-        KE, DN = -(-(de + 3 + dn) // 16) * 16, -(-dn // 16) * 16
-        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        hh, h = self.hid_dim, self._hid_packed()   # h: the packed (padded) width
         d_emb = d_emb.to(dev, torch.float32)
         if h != hh:   # the padded units' columns: zero gradient
             d = d_emb.new_zeros((G, B, h))
             d[:, :, :hh] = d_emb[:, :, :hh]
             d_emb = d
         d_emb = d_emb.contiguous()
-        b = dict(dY2=e(n, h), H1d=e(n, h), dH1=e(n, h), O=e(n, 2 * h), dP=e(n, 2 * h), dQ=e(2, n, 2 * h),
-                 dF=e(n, 3, 2 * h), ev=e(R, KE), AB=e(R, 2, DN), H=e(R, 2, h), dZ=e(R, 2, h), dlev=e(R, DN), g=e(R, DN),
-                 dt=e(R))
-        io = L.EncoderGradIO(*[b[k].data_ptr() if k in b else None for k in L.GRAD_IO_FIELDS])
+        keep, io = self._grad_io(G * B * W, pool=True)
         L.check(L.lib().tm_encoder_pool_bwd(w, L.ptr(nt), L.ptr(et), G, B, W, L.ptr(node6), L.ptr(eid3), L.ptr(ts3),
                                             L.ptr(cat), L.ptr(cut), L.ptr(cnt), L.ptr(wgt), L.ptr(drop), drop_scale,
                                             L.ptr(ws), L.ptr(d_emb), int(d_emb.shape[2]), L.C.byref(io),
                                             L.stream_ptr(dev)), "enhance_predict_walks backward")
-        grads = [e(*s) for s in self._padded_shapes(_POOL_IDX)]
-        gp = (L.C.c_void_p * len(grads))(*[t.data_ptr() for t in grads])
-        L.check(L.lib().tm_encoder_pool_wgrad(w, G, B, W, L.C.byref(io), L.ptr(ws), gp, L.stream_ptr(dev)),
-                "enhance_predict_walks weight gradients")
-        return tuple(self._unpad_grads(grads, _POOL_IDX))
+        return self._wgrad(L.lib().tm_encoder_pool_wgrad, _POOL_IDX, (G, B, W), io, ws,
+                           "enhance_predict_walks weight gradients")
 
     def _enhance_train(self):
         """The HIP training path serves a module on a HIP device whose encoder parameters take gradients, when one

@@ -36,7 +36,7 @@ def dispatch(de, dn=EW.DN):
       (ef_step).
     * encoder.hip, launch_edge_tables: with a table gate_reg_kernel<13, 3, nqe> (q0 == 2) or <22, 11, nqe>; without
       one gate_reg_kernel<d1.nq> for d1.nq in (11, 12, 13, 22) (launch_gate_reg), else the LDS gate_table_kernel.
-    * encoder_train.hip, gcn_bwd_uses_reg / launch_gcn_fwd_reg: the register-resident event_gcn kernels at Q = nqe
+    * encoder_train.hip, gcn_reg_dims / gcn_reg_pick: the register-resident event_gcn kernels at Q = nqe
       when r16(dn) == 176, dn % 4 == 0, de % 4 == 0 and 11 <= nqe <= 14, else the LDS-tiled ones.
     """
     kev, kdep = de + 3 + dn, de + dn

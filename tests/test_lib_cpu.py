@@ -100,6 +100,34 @@ def test_encoder_workspace_sizes():
             assert L.tm_encoder_pool_train_workspace_bytes(w, n) == pool, (h, n)
 
 
+def test_encoder_train_supported_is_pinned():
+    """tm_encoder_train_supported decides whether Python takes the HIP training path at all; it is a pure host
+    function (no device), and its answers over edge_dim x node_dim x hid_dim x if_cat are pinned here: per
+    (hid_dim, cat) one digit per (de, dn), de-major.  hid_dim must be a multiple of 16 up to 256; past that the
+    three LDS sizes decide.  Both answers occur with head_bwd_kernel's tile the only one deciding (hid_dim 192
+    against 256, and 208 with and without the category columns) and with gcn_bwd_kernel's (dn 176 against 1024 at
+    hid_dim 64).  The gate's tile can never be the only one over the budget: its bytes, 128 (r16(de + dn) + r16(h) +
+    r16(h / 2) + 24), are below gcn_bwd_kernel's, at least 128 (r16(de + 3 + dn) + 8) + 256 (r16(dn) + 8) +
+    256 (h + 8), for every h >= 16 -- so no grid shows it deciding, and it is pinned through the other two."""
+    import tempme_amd
+    L = tempme_amd.lib()
+    DE, DN = (1, 4, 32, 172, 512, 4096), (4, 172, 176, 1024, 8192)
+    none = "0" * 30
+    want = {
+        (0, 0): none, (0, 1): none, (8, 0): none, (8, 1): none,
+        (16, 0): "111001110011100111001110000000", (16, 1): "111001110011100111001110000000",
+        (32, 0): "111001110011100111001110000000", (32, 1): "111001110011100111001110000000",
+        (64, 0): "111001110011100111001000000000", (64, 1): "111001110011100111001000000000",
+        (128, 0): "111001110011100111001000000000", (128, 1): "111001110011100111001000000000",
+        (192, 0): "111001110011100111001000000000", (192, 1): "111001110011100111001000000000",
+        (208, 0): "100001000010000100001000000000", (208, 1): none,
+        (256, 0): none, (256, 1): none, (272, 0): none, (272, 1): none,
+    }
+    for (h, cat), row in want.items():
+        got = "".join(str(L.tm_encoder_train_supported(de, dn, h, cat)) for de in DE for dn in DN)
+        assert got == row, (h, cat, got)
+
+
 def test_dropin_extension_loads(monkeypatch):
     """The drop-in fast path's C++ host side (csrc/dropin_ext.cpp, built by build(), used whenever it is built)
     imports on the CPU and exposes its entry points (constructing one needs a HIP device)."""

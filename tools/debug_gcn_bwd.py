@@ -25,15 +25,9 @@ def main(h):
     args = (t(node6), t(eid3), t(ts3), t(cat), t(cut).double(), t(cnt), G, B, W)
     out, ws = ex._train_fwd(args, None, 1.0)
     n = G * B * W
-    R = 3 * n
     dn = ex.node_dim
     kev = de + 3 + dn
-    KE, DN, KM = -(-kev // 16) * 16, -(-dn // 16) * 16, -(-ex.mlp_dim // 16) * 16
-    e = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)  # noqa: E731
-    b = dict(imp=None, dlogit=e(n), M2=e(n, h), dM2=e(n, h), M1d=e(n, KM), dM1=e(n, KM), X=e(n, KM), dY2=e(n, h),
-             H1d=e(n, h), dH1=e(n, h), O=e(n, 2 * h), dP=e(n, 2 * h), dQ=e(2, n, 2 * h), dF=e(n, 3, 2 * h),
-             ev=e(R, KE), AB=e(R, 2, DN), H=e(R, 2, h), dZ=e(R, 2, h), dlev=e(R, DN), g=e(R, DN), dt=e(R))
-    io = L.EncoderGradIO(*[None if b[k] is None else b[k].data_ptr() for k in L.GRAD_IO_FIELDS])
+    b, io = ex._grad_io(n)
     d_imp = torch.from_numpy(np.random.RandomState(4).uniform(-1, 1, n).astype(np.float32)).to(dev)
     nt, et = ex.feature_tables()
     L.check(L.lib().tm_encoder_bwd(ex.packed_weights(), L.ptr(nt), L.ptr(et), G, B, W, L.ptr(args[0]), L.ptr(args[1]),

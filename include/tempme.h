@@ -793,6 +793,44 @@ int tm_ranked_edges(const float *imp1, const float *imp2, const int32_t *node1, 
                     float *out_score, int32_t *out_slot, int32_t *out_mult, int32_t *out_count, int32_t *err_flag,
                     void *stream);
 
+/* Ranked motif instances: the distinct temporal motifs behind a prediction, best first, from the per-walk scores of
+ * TempME.forward (the reference's visualize_explanations.py stops at printing graphlet_imp[0][0:5]).  Walks by row:
+ * eid3 [rows, W, 3], cat [rows, W] (the 12 anonymised categories, 0..11), imp [rows, W].  group_rows
+ * [n_groups, rows_per_group] (1 or 2 rows, -1 = no row) names each group's rows; its entries are their walks in that
+ * order, entry p * W + w.  An entry is live iff eid3[row, w, 0] > 0 (the walk left its root; padding walks are all
+ * zero) and 0 <= cat < 12.  A motif instance is a distinct ordered triple (e0, e1, e2) among the live entries: all 96
+ * bits are compared, later positions may be 0.  Per group, every instance once:
+ *   score = the maximum over its live entries (fp32 comparison, -0 == +0, a NaN loses to every number; the stored
+ *           bits are that entry's, except that a zero maximum is +0.0 and an all-NaN one 0x7FC00000)
+ *   walk  = its lowest live entry index     mult = the number of its live entries     cat = the category of entry walk
+ * ordered by score descending (NaN last), equal scores by the triple ascending (lexicographic, ids as unsigned).
+ * out_eid [n_groups, k, 3] and out_score / out_walk / out_mult / out_cat [n_groups, k] hold the first k; positions
+ * j >= min(count, k) hold eids 0, score 0, walk -1, mult 0, cat -1; out_count [n_groups] = the distinct live
+ * instances (may exceed k).  Category profile over the group's live ENTRIES, [n_groups, 12]: cat_n their number,
+ * cat_max their maximum score (the rules of score; 0 when cat_n is 0), cat_sum the fp64 sum of (double)imp over those
+ * with a non-NaN score, added in ascending entry order by one accumulator.
+ * Comparisons only apart from that sum, no atomics: the same bits from every launch.
+ * A category outside 0..11 sets *err_flag (nullable device int32) to TM_E_ARG and its walk counts as dead; a
+ * group_rows value outside [-1, rows) sets it too and counts as no row.
+ * rows_per_group * W > 1024: TM_E_UNSUPPORTED; k < 1 or k > rows_per_group * W, W < 1, rows_per_group outside
+ * {1, 2}: TM_E_ARG; n_groups = 0 is a no-op.  A refused call writes nothing. */
+int tm_ranked_motifs(const int32_t *eid3, const int32_t *cat, const float *imp, int32_t rows, int32_t W,
+                     const int32_t *group_rows, int32_t n_groups, int32_t rows_per_group, int32_t k,
+                     int32_t *out_eid, float *out_score, int32_t *out_walk, int32_t *out_mult, int32_t *out_cat,
+                     int32_t *out_count, int32_t *cat_n, float *cat_max, double *cat_sum, int32_t *err_flag,
+                     void *stream);
+
+/* The node records a base model scores when only the events of a row's top m motifs are kept.  ranked_eid
+ * [rows, k, 3] and count [rows]: tm_ranked_motifs' out_eid and out_count of a per-row ranking (one group per row);
+ * node, eid [rows, ne]: the subgraph slot records (hop-1 | hop-2 side by side, or hop-1 alone); m_list: n_m values
+ * in HOST memory, each in [1, k].  node_out [n_m, rows, ne]: a slot keeps its node id iff that id is nonzero and its
+ * edge id is positive and equals one of the nonzero ids in the first min(m, count[row], k) triples of its row; every
+ * other slot is 0.  Comparisons only.  k outside [1, 1024], ne < 1, n_m outside [1, 64], an m outside [1, k]:
+ * TM_E_ARG; rows = 0 is a no-op. */
+int tm_motif_mask(const int32_t *ranked_eid, const int32_t *count, int32_t rows, int32_t k, const int32_t *node,
+                  const int32_t *eid, int32_t ne, const int32_t *m_list, int32_t n_m, int32_t *node_out,
+                  void *stream);
+
 /* ---------------------------------------------------------------- per-kernel timing
  * tm_profile_enable(1) clears and starts recording a HIP event pair around every kernel
  * launch, on that launch's stream; tm_profile_sync() waits and aggregates, returning the

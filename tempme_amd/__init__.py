@@ -17,6 +17,7 @@ from .metrics import rank_metrics  # noqa: F401
 from .null_model import degree_dict, get_null_distribution, load_data_shuffle  # noqa: F401
 from .preprocess import calculate_edge, marginal, pre_processing  # noqa: F401
 from .ranked_edges import RankedEdges, ranked_edges  # noqa: F401
+from .ranked_motifs import RankedMotifs, ranked_motifs  # noqa: F401
 from .tgat import TGAT  # noqa: F401
 
 __version__ = "0.1.0"

@@ -53,16 +53,13 @@ def _pair_scores(base_model, emb, G, B):
     return score[:, :B], score[:, B:]
 
 
-def masked_contrast(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src, subgraph_tgt,
-                    subgraph_bgd, n_degree, ratios, side_segments=False):
-    """(pos [G, B], neg [G, B]) logits of contrast on the masked subgraph of every ratio: [hop-1 | hop-2] records
-    masked, then contrast without weights, all ratios in one batch.  ``explanation``: (hop-1 [3B, N], hop-2
-    [3B, N^2]).  ``side_segments`` (tgat): every (ratio, side) is one forward_msg call of B rows, a segment of its
-    own; else (tgn) a ratio's three sides are one segment."""
+def _contrast_nodes(base_model, masked, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, sgs, N, side_segments=False):
+    """(pos [G, B], neg [G, B]) logits of contrast without weights on G masked copies of the batch, all in one
+    batch: ``masked`` [G, 3B, N + N^2] int32 node records ([hop-1 | hop-2]); edge ids and times are the batch's own.
+    ``side_segments`` (tgat): every (copy, side) is one forward_msg call of B rows, a segment of its own; else (tgn)
+    a copy's three sides are one segment."""
     dev = base_model._dev()
-    B, N, G = len(src_l_cut), n_degree, len(ratios)
-    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
-    masked = _masked_nodes(explanation, sgs, N, ratios, dev)                          # [G, 3B, ne]
+    B, G = len(src_l_cut), masked.shape[0]
     roots, _, eids, times = stack_sides(dev, (src_l_cut, dst_l_cut, dst_l_fake), sgs, nodes=False)
     n1 = masked[:, :, :N].reshape(G * 3 * B, N)
     n2 = masked[:, :, N:].reshape(G * 3 * B, N * N)
@@ -72,18 +69,36 @@ def masked_contrast(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, t
     return _pair_scores(base_model, emb, G, B)
 
 
-def masked_contrast_graphmixer(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
-                               subgraph_tgt, subgraph_bgd, n_degree, ratios):
-    """graphmixer branch (temp_exp_main.py:186-206): hop-1 records masked, all ratios in one batch."""
+def _contrast_nodes_graphmixer(base_model, masked, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, sgs, N):
+    """_contrast_nodes for the one-hop GraphMixer base: ``masked`` [G, 3B, N] hop-1 node records."""
     dev = base_model._dev()
-    B, N, G = len(src_l_cut), n_degree, len(ratios)
-    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
-    masked = _masked_nodes(explanation, sgs, N, ratios, dev, hops=1).reshape(G * 3 * B, N)
+    B, G = len(src_l_cut), masked.shape[0]
+    masked = masked.reshape(G * 3 * B, N)
     roots, _, (eid,), (t,) = stack_sides(dev, (src_l_cut, dst_l_cut, dst_l_fake), sgs, nodes=False, hops=1,
                                          idx_dtype=torch.long)
     cut = as_dev(ts_l_cut, dev, torch.float64).reshape(-1).repeat(3 * G)
     emb = base_model.node_embeddings(roots.repeat(G), cut, masked, eid.repeat(G, 1), t.repeat(G, 1))
     return _pair_scores(base_model, emb, G, B)
+
+
+def masked_contrast(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src, subgraph_tgt,
+                    subgraph_bgd, n_degree, ratios, side_segments=False):
+    """(pos [G, B], neg [G, B]) logits of contrast on the masked subgraph of every ratio: [hop-1 | hop-2] records
+    masked, then contrast without weights, all ratios in one batch.  ``explanation``: (hop-1 [3B, N], hop-2
+    [3B, N^2]).  ``side_segments`` (tgat): every (ratio, side) is one forward_msg call of B rows, a segment of its
+    own; else (tgn) a ratio's three sides are one segment."""
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    masked = _masked_nodes(explanation, sgs, n_degree, ratios, base_model._dev())     # [G, 3B, ne]
+    return _contrast_nodes(base_model, masked, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, sgs, n_degree,
+                           side_segments)
+
+
+def masked_contrast_graphmixer(base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
+                               subgraph_tgt, subgraph_bgd, n_degree, ratios):
+    """graphmixer branch (temp_exp_main.py:186-206): hop-1 records masked, all ratios in one batch."""
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    masked = _masked_nodes(explanation, sgs, n_degree, ratios, base_model._dev(), hops=1)
+    return _contrast_nodes_graphmixer(base_model, masked, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, sgs, n_degree)
 
 
 def masked_contrast_tgat(base_model, explanation, *batch):
@@ -124,14 +139,7 @@ def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fa
     with torch.no_grad():
         pos, neg = fns[args.base_type](base_model, explanation, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut,
                                        subgraph_src, subgraph_tgt, subgraph_bgd, args.n_degree, list(args.ratios))
-        po = pos_out_ori.reshape(1, -1).to(pos.device, torch.float32)
-        no = neg_out_ori.reshape(1, -1).to(pos.device, torch.float32)
-        fid_prob = torch.cat([pos.sigmoid() - po.sigmoid(), no.sigmoid() - neg.sigmoid()], dim=1).mean(1)
-        fid_logit = torch.cat([pos - po, no - neg], dim=1).mean(1)
-        y_pred = torch.cat([pos, neg], dim=1).sigmoid()
-        pred_label = torch.where(y_pred > 0.5, 1., 0.)
-        y = y_ori.reshape(1, -1).to(pos.device, torch.float32)
-        acc = (pred_label == y).float().mean(1)
+        fid_prob, fid_logit, y_pred, y, acc = _fidelity_terms(pos, neg, pos_out_ori, neg_out_ori, y_ori)
         if device_metrics:
             from .metrics import rank_metrics
             m = rank_metrics(y.reshape(-1), y_pred).mean(0)
@@ -141,3 +149,97 @@ def threshold_test(args, explanation, base_model, src_l_cut, dst_l_cut, dst_l_fa
     auc = [roc_auc_score(y_h, p) for p in y_pred_h]
     return (float(np.mean(aps)), float(np.mean(auc)), float(acc.mean().item()), float(fid_prob.mean().item()),
             float(fid_logit.mean().item()))
+
+
+def _fidelity_terms(pos, neg, pos_out_ori, neg_out_ori, y_ori):
+    """The per-copy terms of threshold_test's figures from the logits (pos, neg) [G, B] of G masked copies:
+    (fid_prob [G], fid_logit [G], y_pred [G, 2B], y [1, 2B], acc [G]), float32 on the logits' device."""
+    po = pos_out_ori.reshape(1, -1).to(pos.device, torch.float32)
+    no = neg_out_ori.reshape(1, -1).to(pos.device, torch.float32)
+    fid_prob = torch.cat([pos.sigmoid() - po.sigmoid(), no.sigmoid() - neg.sigmoid()], dim=1).mean(1)
+    fid_logit = torch.cat([pos - po, no - neg], dim=1).mean(1)
+    y_pred = torch.cat([pos, neg], dim=1).sigmoid()
+    pred_label = torch.where(y_pred > 0.5, 1., 0.)
+    y = y_ori.reshape(1, -1).to(pos.device, torch.float32)
+    acc = (pred_label == y).float().mean(1)
+    return fid_prob, fid_logit, y_pred, y, acc
+
+
+def _fidelity_rows(pos, neg, pos_out_ori, neg_out_ori, y_ori, device_metrics=False):
+    """threshold_test's five figures (AP, AUC, accuracy, fidelity of probabilities and of logits) of every masked
+    copy on its own, float64 [G, 5]: a device tensor with ``device_metrics`` (one rank_metrics launch, nothing waits
+    for the device), else numpy with AP and AUC from scikit-learn."""
+    fid_prob, fid_logit, y_pred, y, acc = _fidelity_terms(pos, neg, pos_out_ori, neg_out_ori, y_ori)
+    tail = torch.stack([acc, fid_prob, fid_logit], dim=1).double()
+    if device_metrics:
+        from .metrics import rank_metrics
+        return torch.cat([rank_metrics(y.reshape(-1), y_pred), tail], dim=1)
+    y_pred_h, y_h = y_pred.cpu().numpy(), y_ori.reshape(-1).cpu().numpy()
+    rank = [[average_precision_score(y_h, p), roc_auc_score(y_h, p)] for p in y_pred_h]
+    return np.concatenate([np.asarray(rank, np.float64).reshape(-1, 2), tail.cpu().numpy()], axis=1)
+
+
+def motif_masked_nodes(ranked_rows, subgraphs, n_degree, m_list, hops=2):
+    """[Gm, 3B, ne] int32 node records that keep only the events of each row's top m motifs, for every m of
+    ``m_list``: one launch of ``tm_motif_mask``.  ``ranked_rows``: the per-row ranking
+    ``ranked_motifs(imp, walks, k, pairs=False)`` with k >= max(m_list); ``subgraphs``: the three sides' (node, eid,
+    time) records; hops=2: [hop-1 | hop-2] records, ne = N + N^2 (tgn, tgat), hops=1: ne = N (graphmixer).  A slot
+    keeps its node id iff its edge id is one of the ids of the first min(m, count) triples of its row."""
+    eid3, count = ranked_rows.eid, ranked_rows.count
+    dev = L.require_device(eid3.device)
+    if eid3.dim() != 3 or eid3.shape[-1] != 3 or count.dim() != 1:
+        raise ValueError(f"motif_masked_nodes: ranked_rows is a per-row ranking (pairs=False), eid "
+                         f"{tuple(eid3.shape)} is not [rows, k, 3]")
+    N = int(n_degree)
+    ne = N + N * N if hops == 2 else N
+    rec = lambda i: torch.cat([torch.cat([as_dev(sg[i][h], dev, torch.int32) for h in range(hops)], dim=1)  # noqa: E731
+                               for sg in subgraphs], dim=0).contiguous()
+    nodes, eids = rec(0), rec(1)
+    rows, k = eid3.shape[0], eid3.shape[1]
+    if tuple(nodes.shape) != (rows, ne) or tuple(eids.shape) != (rows, ne):
+        raise ValueError(f"motif_masked_nodes: subgraph records {tuple(nodes.shape)} do not match the ranking's "
+                         f"({rows}, {ne})")
+    ms = [int(m) for m in m_list]
+    if not ms or min(ms) < 1 or max(ms) > k:
+        raise ValueError(f"motif_masked_nodes: m_list {ms} is outside [1, {k}], the ranked motifs of a row")
+    m_host = np.asarray(ms, dtype=np.int32)
+    out = torch.empty((len(ms), rows, ne), dtype=torch.int32, device=dev)
+    L.check(L.lib().tm_motif_mask(L.ptr(eid3.contiguous()), L.ptr(count.contiguous()), rows, k, L.ptr(nodes),
+                                  L.ptr(eids), ne, m_host.ctypes.data, len(ms), L.ptr(out), L.stream_ptr(dev)),
+            "motif_masked_nodes")
+    return out
+
+
+def motif_masked_contrast(args, imp, walks, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, subgraph_src,
+                          subgraph_tgt, subgraph_bgd, m_list, k=None):
+    """(pos [Gm, B], neg [Gm, B]) logits of contrast on the subgraphs that keep only the events of every row's top m
+    motifs, all m of ``m_list`` in one batch (as masked_contrast* does for ratios): the rows are ranked
+    (``ranked_motifs(imp, walks, k, pairs=False)``, k = max(m_list) by default), masked (``motif_masked_nodes``) and
+    scored without weights."""
+    from .ranked_motifs import ranked_motifs
+    if args.base_type not in ("tgn", "graphmixer", "tgat"):
+        raise NotImplementedError(f"motif_threshold_test for base_type {args.base_type!r}: tgn, graphmixer and tgat "
+                                  "are built")
+    ms = [int(m) for m in m_list]
+    sgs = (subgraph_src, subgraph_tgt, subgraph_bgd)
+    hops = 1 if args.base_type == "graphmixer" else 2
+    ranked = ranked_motifs(imp, walks, max(ms) if k is None else int(k), pairs=False)
+    masked = motif_masked_nodes(ranked, sgs, args.n_degree, ms, hops)
+    batch = (src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, sgs, args.n_degree)
+    if hops == 1:
+        return _contrast_nodes_graphmixer(base_model, masked, *batch)
+    return _contrast_nodes(base_model, masked, *batch, side_segments=args.base_type == "tgat")
+
+
+def motif_threshold_test(args, imp, walks, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut, e_l_cut,
+                         pos_out_ori, neg_out_ori, y_ori, subgraph_src, subgraph_tgt, subgraph_bgd, m_list, k=None,
+                         device_metrics=False):
+    """threshold_test at the motif level: for every m of ``m_list`` only the events of each row's top m motif
+    instances stay in the subgraphs and the base model is scored again against its original predictions.  Returns
+    threshold_test's five figures (AP, AUC, accuracy, fidelity of probabilities and of logits) per m, not averaged:
+    float64 [Gm, 5], a device tensor with ``device_metrics``, else numpy.  ``imp``, ``walks``: the walk scores and
+    the walks as ``ranked_motifs`` takes them; the batch arguments are threshold_test's."""
+    with torch.no_grad():
+        pos, neg = motif_masked_contrast(args, imp, walks, base_model, src_l_cut, dst_l_cut, dst_l_fake, ts_l_cut,
+                                         subgraph_src, subgraph_tgt, subgraph_bgd, m_list, k)
+        return _fidelity_rows(pos, neg, pos_out_ori, neg_out_ori, y_ori, device_metrics)

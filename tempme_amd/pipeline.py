@@ -186,6 +186,16 @@ class ExplainPipeline:
         return ranked_edges([self.h1[:3 * E * N].view(3 * E, N), self.h2[:3 * E * N * N].view(3 * E, N * N)], sgs,
                             (src, dst, b.dst_fake[:E]), k, pairs=pairs)
 
+    def ranked_motifs(self, k, pairs=True):
+        """The distinct motif instances behind each of the last call's predictions, best first, with the
+        predictions' category profiles (ranked_motifs.RankedMotifs), from the pipeline's own walk scores and walk
+        buffers after ``run()``: [2, E, ...] with ``pairs``, else [3E, ...].  One launch on the current stream."""
+        from .ranked_motifs import ranked_motifs
+        if self._E is None or getattr(self, "_roots", None) is None:
+            raise RuntimeError("ExplainPipeline.ranked_motifs: nothing has run yet")
+        E, W, b = self._E, self.W, self.buf
+        return ranked_motifs(self.imp[:3 * E * W].view(3, E, W), (b.node6, b.eid3, b.ts3, b.cat), k, pairs=pairs)
+
     def check_errors(self):
         if getattr(self, "buf", None) is not None:   # nothing sampled yet: nothing to report
             L.raise_device_error(int(self.buf.err.item()), "ExplainPipeline")

@@ -212,6 +212,15 @@ void tm_weight_split3(const float *in, int64_t n, uint16_t *hi, uint16_t *mid, u
  * is >= nout or the column >= dn. */
 void tm_weight_gcn_split(const float *w, int32_t nout, int32_t dn, uint16_t *out);
 
+/* lin_event's split pack that the walk kernel multiplies with on bf16 MFMA, built on the host exactly as
+ * tm_weights_pack builds it on the device, from a row-major w[nout][kev].  Tile-major: for each of the
+ * nt = ceil(nout / 16) output tiles its ns = ceil(kev / 32) K steps, each step's hi / mid / lo fragments (parts of
+ * tm_weight_split3) one after the other.  A 32-wide step's fragment is 512 bf16 bit patterns, element lane * 8 + j =
+ * w[16 t + (lane & 15)][32 s + 8 (lane >> 4) + j].  When 1 <= kev mod 32 <= 16 the last step is 16 deep: its
+ * fragments are 256 bf16, element lane * 4 + j = w[16 t + (lane & 15)][32 s + 4 (lane >> 4) + j].  Zero where the
+ * row is >= nout or the column >= kev.  Returns the pack's size in bf16; out == NULL asks for the size alone. */
+int64_t tm_weight_lin_split(const float *w, int32_t nout, int32_t kev, uint16_t *out);
+
 /* Workspace bytes tm_encoder_fwd needs for n_walks walks. */
 int64_t tm_encoder_workspace_bytes(const tm_weights *w, int64_t n_walks);
 

@@ -38,7 +38,7 @@ EXPORTS = (
     "tm_graph_strict_view",
     "tm_sample_khop", "tm_sample_walks", "tm_neg_sample", "tm_perm_keys", "tm_motif_hist", "tm_edge_counts",
     "tm_sample_events", "tm_gather_rows", "tm_weights_create", "tm_weights_create_ex", "tm_weights_pack", "tm_weights_variant", "tm_weights_set_node_zero", "tm_weights_version", "tm_weights_free",
-    "tm_weight_split3", "tm_weight_gcn_split", "tm_encoder_workspace_bytes",
+    "tm_weight_split3", "tm_weight_gcn_split", "tm_weight_lin_split", "tm_encoder_workspace_bytes",
     "tm_walk_importance", "tm_encoder_pool_workspace_bytes", "tm_encoder_pool_fwd",
     "tm_encoder_pool_train_workspace_bytes", "tm_encoder_pool_train_fwd", "tm_encoder_pool_bwd", "tm_encoder_pool_wgrad",
     "tm_encoder_fwd", "tm_encoder_fwd_tab", "tm_encoder_train_supported", "tm_encoder_train_fwd", "tm_encoder_bwd", "tm_encoder_wgrad", "tm_wgrad",
@@ -166,6 +166,8 @@ def _sig(L):
     L.tm_weights_free.argtypes = [vp]
     L.tm_weight_split3.argtypes = [vp, i64, vp, vp, vp]
     L.tm_weight_gcn_split.argtypes = [vp, i32, i32, vp]
+    L.tm_weight_lin_split.restype = i64
+    L.tm_weight_lin_split.argtypes = [vp, i32, i32, vp]
     L.tm_encoder_workspace_bytes.restype = i64
     L.tm_encoder_workspace_bytes.argtypes = [vp, i64]
     L.tm_encoder_fwd.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -258,7 +260,7 @@ def _sig(L):
     L.tm_beta_rsample_bwd.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp]
     L.tm_profile_entry.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.POINTER(i64)]
     for name in EXPORTS:
-        if name not in ("tm_last_error", "tm_encoder_workspace_bytes", "tm_encoder_pool_workspace_bytes",
+        if name not in ("tm_last_error", "tm_weight_lin_split", "tm_encoder_workspace_bytes", "tm_encoder_pool_workspace_bytes",
                         "tm_encoder_pool_train_workspace_bytes", "tm_gm_train_workspace_bytes",
                         "tm_tgat_attn_train_workspace_bytes", "tm_tgn_attn_train_workspace_bytes"):
             getattr(L, name).restype = C.c_int

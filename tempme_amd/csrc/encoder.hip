@@ -825,7 +825,12 @@ __device__ __forceinline__ void cgemm2(__amdgpu_buffer_rsrc_t wr, const floatx4 
 // four register moves).
 template <int NQE, int NTD>
 struct WalkConsts {
-    static constexpr int NS = (NQE + 1) / 2;   // lin_event's 32-wide K steps (XW / XP padded to them)
+    static constexpr int NS = (NQE + 1) / 2;   // lin_event's K steps (XW / XP padded to 32 entries each)
+    // an odd count of 16-feature quads (1 <= kev mod 32 <= 16, ev3_tail): the last step is 16 deep, each lane
+    // generating 4 features for it and reading 8-byte weight fragments (Ev3Lay)
+    static constexpr bool TAIL = NQE % 2 == 1;
+    // byte offset of fragment (tile t, step s, part) in the split pack EncW::ev3
+    static constexpr int ev3_byte(int t, int s, int part) { return 2 * Ev3Lay(NS, TAIL).frag(t, s, part); }
     static constexpr int XW = 0, XP = XW + 32 * NS, EV = XP + 32 * NS, EVC = EV + 16 * NTD, DEVC = EVC + 16 * NTD,
                          G1 = DEVC + 16 * NTD, G1C = G1 + HID, V0 = G1C + HID, CP = V0 + 2 * HID,
                          U = CP + HID, M2 = U + 2 * HID, M3 = M2 + HID, TC = M3 + HID, M3B = TC + 13 * 80,
@@ -992,12 +997,35 @@ __device__ __forceinline__ void split_put(Split3 &x, int j, float v) {
     x.l[j] = (__bf16)(r - (float)m);
 }
 #define TM_MF32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0)
+// One product of a lin_event K step: a 32-wide step on v_mfma_f32_16x16x32_bf16, the pack's 16-deep last step (t16,
+// WalkConsts::TAIL; known at compile time once the K loop is unrolled) on v_mfma_f32_16x16x16_bf16 over elements
+// 0..3 of both operands -- lane group g's k = 4g + 0..3 in A and B alike, the same D tile.
+typedef short shortx4 __attribute__((ext_vector_type(4)));
+typedef unsigned int uintx2 __attribute__((ext_vector_type(2)));
+// a half-size (16-deep) fragment: 8 bytes per lane
+__device__ __forceinline__ float2 wload_half(__amdgpu_buffer_rsrc_t r, int vo, int so) {
+    const uintx2 v = __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0);
+    return __builtin_bit_cast(float2, v);
+}
+__device__ __forceinline__ floatx4 mf_lin(bool t16, const bf16x8 &a, const bf16x8 &b, const floatx4 &c) {
+    if (t16) {
+        const shortx4 a4 = __builtin_bit_cast(shortx4, __builtin_shufflevector(a, a, 0, 1, 2, 3));
+        const shortx4 b4 = __builtin_bit_cast(shortx4, __builtin_shufflevector(b, b, 0, 1, 2, 3));
+        return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a4, b4, c, 0, 0, 0);
+    }
+    return TM_MF32(a, b, c);
+}
 
 // this lane's 8 entries of 32-wide K step s of an LDS vector laid out on the event-feature axis
 __device__ __forceinline__ void lds8(const float *v, int s, float (&o)[8]) {
     const float4 *p = reinterpret_cast<const float4 *>(v + 32 * s + 8 * ((threadIdx.x & 63) >> 4));
     const float4 a = p[0], b = p[1];
     o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w, o[4] = b.x, o[5] = b.y, o[6] = b.z, o[7] = b.w;
+}
+// the same for a 16-deep step starting at feature 32s: this lane's 4 entries (o[0..3]; o[4..7] untouched)
+__device__ __forceinline__ void lds4k(const float *v, int s, float (&o)[8]) {
+    const float4 a = *reinterpret_cast<const float4 *>(v + 32 * s + 4 * ((threadIdx.x & 63) >> 4));
+    o[0] = a.x, o[1] = a.y, o[2] = a.z, o[3] = a.w;
 }
 
 // Element j of K step s of the event features x[k] = [E(e) | cnt | cos(dt * w + phi)] (:176-179,
@@ -1007,14 +1035,15 @@ __device__ __forceinline__ void lds8(const float *v, int s, float (&o)[8]) {
 // opaque asm keeps the compiler from wrapping the polynomial in an exec-mask branch, which serialised it
 // against the MFMAs) and the count / edge lanes select their values.  Padding lanes (k >= kev) keep
 // cos(0) = 1: lin_event's packed weights are zero there.  In table mode the edge lanes are 0 (their product
-// comes from the table row).
+// comes from the table row).  t16: the 16-deep last step, k = 32s + 4g + j (j < 4); it starts past the edge
+// features and the counts in every instance (walk_pick), so e is not used there.
 template <bool ETAB, bool PURE>
 __device__ __forceinline__ float gen_one(int s, int j, float w, float ph, float e, int g, int de, float dt, float c0,
-                                         float c1, float c2) {
+                                         float c1, float c2, bool t16 = false) {
     if (!ETAB && !PURE && 32 * s + 32 <= de) return e;   // a step of edge features alone (wave-uniform)
     float c = time_cos(dt, w, ph);
     if constexpr (PURE) return c;
-    const int k = 32 * s + 8 * g + j;
+    const int k = 32 * s + (t16 ? 4 : 8) * g + j;
     asm volatile("" : "+v"(c));
     float v = c;
     if (k < de + 3) v = (k == de) ? c0 : (k == de + 1) ? c1 : c2;
@@ -1210,25 +1239,38 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         rt[q % JN] = nrow_t[f4];
     };
     {
-        constexpr int NS = C::NS, S0 = Q0 / 2;           // 32-wide K steps; table mode starts at step de / 32
+        constexpr int NS = C::NS, S0 = Q0 / 2;           // K steps; table mode starts at step de / 32
         constexpr int N = NTD * (NS - S0) * 3, D = 12;   // fragments (tile, step, part); ring depth: 4 (tile, step)s
         static_assert(D >= PFP && D <= N && D % 3 == 0, "lin_event ring depth");
         static_assert(D == GD, "the zero-node event_gcn takes over lin_event's ring slots");
+        static_assert(!C::TAIL || N >= D + 3 * NTD, "the 16-deep step is not in the ring's first fill");
         const int vo = lane_id() * 16;
         // the split pack's byte offset off wr in the lane offset, so every fragment offset stays a constant
         const int vo3 = vo + 16 * (int)(P.ev3 - P.kv.w);
         // ring order K-outer: fragment i = (step S0 + i / (3 NTD), tile (i / 3) % NTD, part i % 3).  The first PFP
         // come in pre, requested during the previous pass; the ring's last refills request event_gcn's first K
-        // step (G1 tiles 0..3; ZN: all D slots take the g13 pack's first streamed pair step)
-        auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
+        // step (G1 tiles 0..3; ZN: all D slots take the g13 pack's first streamed pair step).  The ring counts
+        // fragments, whatever their size: a half-size fragment of the 16-deep step (C::TAIL, t16) is one fragment
+        // like the others, takes one slot and fills its low 8 bytes with a 64-bit load at the lane offset vo3h.
+        auto t16 = [](int i) { return C::TAIL && S0 + i / (3 * NTD) == NS - 1; };
+        auto off = [](int i) { return C::ev3_byte((i / 3) % NTD, S0 + i / (3 * NTD), i % 3); };
+        const int vo3h = vo3 - (vo >> 1);
         auto g1f = [](int k) { return LY::G1 / 4 + k * NTD * 64; };
         // the constant rides on an opaque scalar zero defined inside the pass loop: the ~200 distinct offsets are
         // then one s_add each where they are used, not hoisted out of the loop into spilled SGPRs (a v_readlane
         // per load on the VALU pipe, which the feature generation needs)
         int z3 = 0;
         asm volatile("" : "+s"(z3));
-        auto wload3 = [&](int i) {
-            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i) * 16, 0));
+        // fragment i into a ring slot (old: the slot's content, whose high half a half-size fragment leaves alone;
+        // the first fill holds full fragments only)
+        auto wload3 = [&](int i, float4 old = float4{}) {
+            if (t16(i)) {
+                const float2 v = wload_half(wr, vo3h, z3 + off(i));
+                old.x = v.x;
+                old.y = v.y;
+                return old;
+            }
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i), 0));
         };
         auto wloadg = [&](int i) {
             return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, z3 + goff(i) * 16, 0));
@@ -1237,7 +1279,9 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         float4 buf[D];
 #pragma unroll
         for (int i = 0; i < D; ++i) buf[i] = i < PFP ? pre[i] : wload3(i);
-        const int qend = p == 2 ? P.qt : NS;             // slot pass: steps >= qt folded into evc / devc
+        // the slot pass runs the steps below qt only (the others are folded into evc / devc); qt counts the steps
+        // that hold an edge feature or a count, and the 16-deep step holds neither: the slot pass never reaches it
+        const int qend = p == 2 ? P.qt : NS;
         // this lane's edge features of step s: plain mode from ef (steps 0, 1), streamed (SEF) through a ring
         // of two steps, step s + 2's requested while step s's MFMAs run; none in table mode
         const float4 *erow4 = reinterpret_cast<const float4 *>(a.e_feat + (int64_t)pi.edge() * de);
@@ -1266,8 +1310,12 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
         for (int s = S0; s < NS; ++s) {
             if (s < qend) {                               // wave-uniform (a break would stop the unrolling)
                 // step s + 1's constants from LDS now (first use after the first tile pair's MFMAs)
+                const bool c16 = C::TAIL && s == NS - 1, n16 = C::TAIL && s + 1 == NS - 1;   // this / the next step 16 deep
                 float w8[8] = {}, p8[8] = {};
-                if (s + 1 < NS) {
+                if (n16) {
+                    lds4k(cw, s + 1, w8);
+                    lds4k(cp, s + 1, p8);
+                } else if (s + 1 < NS) {
                     lds8(cw, s + 1, w8);
                     lds8(cp, s + 1, p8);
                 }
@@ -1280,18 +1328,19 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
                 }
                 Split3 xn = xs;
                 // element j of step s + 1, generated and split between this step's MFMAs (one per tile, tiles 0..7)
+                // (a 16-deep step: 4 elements per lane, generated beside tiles 0..3)
                 auto gen = [&](int j) {
-                    if (s + 1 < NS && j < 8) {
-                        const float e = edge(s + 1, j);
-                        const float v = pure(s + 1) ? gen_one<ETAB, true>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2)
-                                                    : gen_one<ETAB, false>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2);
+                    if (s + 1 < NS && j < (n16 ? 4 : 8)) {
+                        const float e = n16 ? 0.f : edge(s + 1, j);
+                        const float v = pure(s + 1) ? gen_one<ETAB, true>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2, n16)
+                                                    : gen_one<ETAB, false>(s + 1, j, w8[j], p8[j], e, g, de, dt, c0, c1, c2, n16);
                         split_put(xn, j, v);
                     }
                 };
                 // fragment i out of the ring; its slot takes fragment i + D (past N: G1's first)
                 auto take = [&](int i) {
                     const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
-                    if (i + D < N) buf[i % D] = wload3(i + D);
+                    if (i + D < N) buf[i % D] = wload3(i + D, buf[i % D]);
                     else if constexpr (RES) {
                         if (i + D - N < PFP) buf[i % D] = wload(wr, vo, nx.o[i + D - N]);
                     } else if constexpr (ZN) buf[i % D] = wloadg(i + D - N);
@@ -1304,18 +1353,18 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
                     const int i = ((s - S0) * NTD + t) * 3;
                     const bf16x8 h0 = take(i), m0 = take(i + 1), l0 = take(i + 2);
                     const bf16x8 h1 = take(i + 3), m1 = take(i + 4), l1 = take(i + 5);
-                    L[t] = TM_MF32(l0, xs.h, L[t]);
-                    L[t + 1] = TM_MF32(l1, xs.h, L[t + 1]);
-                    L[t] = TM_MF32(h0, xs.l, L[t]);
-                    L[t + 1] = TM_MF32(h1, xs.l, L[t + 1]);
-                    L[t] = TM_MF32(m0, xs.m, L[t]);
-                    L[t + 1] = TM_MF32(m1, xs.m, L[t + 1]);
-                    L[t] = TM_MF32(m0, xs.h, L[t]);
-                    L[t + 1] = TM_MF32(m1, xs.h, L[t + 1]);
-                    L[t] = TM_MF32(h0, xs.m, L[t]);
-                    L[t + 1] = TM_MF32(h1, xs.m, L[t + 1]);
-                    L[t] = TM_MF32(h0, xs.h, L[t]);
-                    L[t + 1] = TM_MF32(h1, xs.h, L[t + 1]);
+                    L[t] = mf_lin(c16, l0, xs.h, L[t]);
+                    L[t + 1] = mf_lin(c16, l1, xs.h, L[t + 1]);
+                    L[t] = mf_lin(c16, h0, xs.l, L[t]);
+                    L[t + 1] = mf_lin(c16, h1, xs.l, L[t + 1]);
+                    L[t] = mf_lin(c16, m0, xs.m, L[t]);
+                    L[t + 1] = mf_lin(c16, m1, xs.m, L[t + 1]);
+                    L[t] = mf_lin(c16, m0, xs.h, L[t]);
+                    L[t + 1] = mf_lin(c16, m1, xs.h, L[t + 1]);
+                    L[t] = mf_lin(c16, h0, xs.m, L[t]);
+                    L[t + 1] = mf_lin(c16, h1, xs.m, L[t + 1]);
+                    L[t] = mf_lin(c16, h0, xs.h, L[t]);
+                    L[t + 1] = mf_lin(c16, h1, xs.h, L[t + 1]);
                     gen(t);
                     gen(t + 1);
                     __builtin_amdgcn_sched_barrier(0);
@@ -1324,12 +1373,12 @@ __device__ __forceinline__ void encode_position(const WalkArgs &a, __amdgpu_buff
                     constexpr int t = NTD - 1;
                     const int i = ((s - S0) * NTD + t) * 3;
                     const bf16x8 h0 = take(i), m0 = take(i + 1), l0 = take(i + 2);
-                    L[t] = TM_MF32(l0, xs.h, L[t]);
-                    L[t] = TM_MF32(h0, xs.l, L[t]);
-                    L[t] = TM_MF32(m0, xs.m, L[t]);
-                    L[t] = TM_MF32(m0, xs.h, L[t]);
-                    L[t] = TM_MF32(h0, xs.m, L[t]);
-                    L[t] = TM_MF32(h0, xs.h, L[t]);
+                    L[t] = mf_lin(c16, l0, xs.h, L[t]);
+                    L[t] = mf_lin(c16, h0, xs.l, L[t]);
+                    L[t] = mf_lin(c16, m0, xs.m, L[t]);
+                    L[t] = mf_lin(c16, m0, xs.h, L[t]);
+                    L[t] = mf_lin(c16, h0, xs.m, L[t]);
+                    L[t] = mf_lin(c16, h0, xs.h, L[t]);
                     gen(t);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1487,14 +1536,24 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
         constexpr int NS = C::NS, S0 = Q0 / 2;
         constexpr int N = NTD * (NS - S0) * 3, D = PAIR_LIN_RING;
         static_assert(D >= PFP && D <= N && D % 3 == 0 && (RES || D <= GD), "lin_event ring depth");
+        static_assert(!C::TAIL || N >= D + 3 * NTD, "the 16-deep step is not in the ring's first fill");
         const int vo = lane_id() * 16;
-        const int vo3 = lane_id() * 16 + 16 * (int)(P.ev3 - P.kv.w);
-        auto off = [](int i) { return ((((i / 3) % NTD) * NS + S0 + i / (3 * NTD)) * 3 + i % 3) * 64; };
+        const int vo3 = vo + 16 * (int)(P.ev3 - P.kv.w);
+        // the 16-deep last step (C::TAIL): half-size fragments, one ring slot each, 64-bit loads at the lane offset vo3h
+        auto t16 = [](int i) { return C::TAIL && S0 + i / (3 * NTD) == NS - 1; };
+        auto off = [](int i) { return C::ev3_byte((i / 3) % NTD, S0 + i / (3 * NTD), i % 3); };
+        const int vo3h = vo3 - (vo >> 1);
         auto goff = [](int i) { return ((((i / 3) % 4) * NSG + GL + i / 12) * 3 + i % 3) * 64; };
         int z3 = 0;
         asm volatile("" : "+s"(z3));
-        auto wload3 = [&](int i) {
-            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i) * 16, 0));
+        auto wload3 = [&](int i, float4 old = float4{}) {
+            if (t16(i)) {
+                const float2 v = wload_half(wr, vo3h, z3 + off(i));
+                old.x = v.x;
+                old.y = v.y;
+                return old;
+            }
+            return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vo3, z3 + off(i), 0));
         };
         auto wloadg = [&](int i) {
             return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wr, vog, z3 + goff(i) * 16, 0));
@@ -1518,24 +1577,26 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
         }
 #pragma unroll
         for (int s = S0; s < NS; ++s) {
+            const bool c16 = C::TAIL && s == NS - 1, n16 = C::TAIL && s + 1 == NS - 1;   // this / the next step 16 deep
             Split3 xn0 = xs0, xn1 = xs1;
             // element j of step s + 1 of both sets, generated and split between this step's MFMAs (tiles 0..7); its
             // frequency and phase are read from LDS where they are used (two sets of step features leave no
-            // registers for a step's 16 constants)
+            // registers for a step's 16 constants).  A 16-deep step: 4 elements per lane, beside tiles 0..3.
             auto gen = [&](int j) {
-                if (s + 1 < NS && j < 8) {
-                    const float w = cw[32 * (s + 1) + 8 * g + j], ph = cp[32 * (s + 1) + 8 * g + j];
-                    const float v0 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02)
-                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02);
-                    const float v1 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12)
-                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12);
+                if (s + 1 < NS && j < (n16 ? 4 : 8)) {
+                    const int k = split_pack_col(1, s + 1, g, j, n16);
+                    const float w = cw[k], ph = cp[k];
+                    const float v0 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02, n16)
+                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt0, c00, c01, c02, n16);
+                    const float v1 = pure(s + 1) ? gen_one<true, true>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12, n16)
+                                                 : gen_one<true, false>(s + 1, j, w, ph, 0.f, g, de, dt1, c10, c11, c12, n16);
                     split_put(xn0, j, v0);
                     split_put(xn1, j, v1);
                 }
             };
             auto take = [&](int i) {
                 const bf16x8 v = __builtin_bit_cast(bf16x8, buf[i % D]);
-                if (i + D < N) buf[i % D] = wload3(i + D);
+                if (i + D < N) buf[i % D] = wload3(i + D, buf[i % D]);
                 else if constexpr (RES) {
                     if (i + D - N < PFP) buf[i % D] = wload(wr, vo, nx.o[i + D - N]);
                 } else buf[i % D] = wloadg(i + D - N);
@@ -1545,18 +1606,18 @@ __device__ __forceinline__ void encode_pair(const WalkArgs &a, __amdgpu_buffer_r
             for (int t = 0; t < NTD; ++t) {
                 const int i = ((s - S0) * NTD + t) * 3;
                 const bf16x8 h = take(i), m = take(i + 1), l = take(i + 2);
-                L0[t] = TM_MF32(l, xs0.h, L0[t]);
-                L1[t] = TM_MF32(l, xs1.h, L1[t]);
-                L0[t] = TM_MF32(h, xs0.l, L0[t]);
-                L1[t] = TM_MF32(h, xs1.l, L1[t]);
-                L0[t] = TM_MF32(m, xs0.m, L0[t]);
-                L1[t] = TM_MF32(m, xs1.m, L1[t]);
-                L0[t] = TM_MF32(m, xs0.h, L0[t]);
-                L1[t] = TM_MF32(m, xs1.h, L1[t]);
-                L0[t] = TM_MF32(h, xs0.m, L0[t]);
-                L1[t] = TM_MF32(h, xs1.m, L1[t]);
-                L0[t] = TM_MF32(h, xs0.h, L0[t]);
-                L1[t] = TM_MF32(h, xs1.h, L1[t]);
+                L0[t] = mf_lin(c16, l, xs0.h, L0[t]);
+                L1[t] = mf_lin(c16, l, xs1.h, L1[t]);
+                L0[t] = mf_lin(c16, h, xs0.l, L0[t]);
+                L1[t] = mf_lin(c16, h, xs1.l, L1[t]);
+                L0[t] = mf_lin(c16, m, xs0.m, L0[t]);
+                L1[t] = mf_lin(c16, m, xs1.m, L1[t]);
+                L0[t] = mf_lin(c16, m, xs0.h, L0[t]);
+                L1[t] = mf_lin(c16, m, xs1.h, L1[t]);
+                L0[t] = mf_lin(c16, h, xs0.m, L0[t]);
+                L1[t] = mf_lin(c16, h, xs1.m, L1[t]);
+                L0[t] = mf_lin(c16, h, xs0.h, L0[t]);
+                L1[t] = mf_lin(c16, h, xs1.h, L1[t]);
                 gen(t);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1844,7 +1905,7 @@ __global__ void __launch_bounds__(64 * walk_wpb(ZN, PAIR, SPLIT, POOL), WALK_WAV
     // step QE0 / 2, in the split pack EncW::ev3), carried pass to pass
     NextFr lin0;
 #pragma unroll
-    for (int k = 0; k < PFP; ++k) lin0.o[k] = (int)(P.ev3 - P.kv.w) + (((k / 3) * C::NS + QE0 / 2) * 3 + k % 3) * 64;
+    for (int k = 0; k < PFP; ++k) lin0.o[k] = (int)(P.ev3 - P.kv.w) + C::ev3_byte(k / 3, QE0 / 2, k % 3) / 16;
     float4 pre[PFP];
 #pragma unroll
     for (int k = 0; k < PFP; ++k) pre[k] = wload(wr, lane_id() * 16, lin0.o[k]);
@@ -2093,7 +2154,10 @@ static bool walk_layout_ok(const EncW &P, int nqe) {
     return at(P.ev.w, ev) && at(P.g1.w, g1) && at(P.m2.w, m2) && at(P.a1d.w, FoldLay::A1D) &&
            at(P.a1g.w, FoldLay::A1G) && at(P.m1a2.w, FoldLay::M1A2) && at(P.kvz.w, FoldLay::KVZ) &&
            at(P.a1dz.w, FoldLay::A1DZ) && at(P.a1gz.w, FoldLay::A1GZ) && P.g1.nt == 4 && P.g1.nq == 11 && P.m2.nt == 4 && P.m2.nq == 5 && P.ev.nt == 11 && P.ev.nq == nqe &&
-           P.ev3 && P.ns3 == (nqe + 1) / 2 && P.g13 && P.nsg == 6;
+           P.ev3 && P.ns3 == (nqe + 1) / 2 && P.g13 && P.nsg == 6 &&
+           // a 16-deep last step holds time features only (gen_one drops the edge value there, and the slot pass,
+           // which stops at qt, never runs it): every step with an edge feature or a count lies before it
+           (!ev3_tail(P.kev) || P.qt <= P.ns3 - 1);
 }
 
 // ------------------------------------------------------------------ per-edge dependency gate table
@@ -2430,10 +2494,10 @@ extern "C" int tm_weights_create_ex(int32_t de, int32_t dn, int32_t h, int32_t i
     const size_t ph = total; total += r16(dn);
     const size_t evc = total; total += r16(dn);
     const size_t devc = total; total += r16(dn);
-    // lin_event's three-way bf16 split pack (EncW::ev3): 3 fragments of 256 floats per (tile, 32-wide K step)
+    // lin_event's three-way bf16 split pack (EncW::ev3): 3 fragments per (tile, K step), Ev3Lay
     const int ns3 = (P.kev + 31) / 32;
     total = (total + 63) & ~(size_t)63;
-    const size_t ev3 = total; total += (size_t)(r16(dn) / 16) * ns3 * 3 * 256;
+    const size_t ev3 = total; total += ((size_t)(r16(dn) / 16) * tmk::Ev3Lay(ns3, tmk::ev3_tail(P.kev)).tile() / 2 + 63) & ~(size_t)63;
     // event_gcn's first layer likewise (EncW::g13): 3 fragments per (output tile, pair step of two input tiles)
     const int nsg = (r16(dn) / 16 + 1) / 2;
     const size_t g13 = total; total += (size_t)(r16(h) / 16) * nsg * 3 * 256;
@@ -2527,6 +2591,22 @@ extern "C" void tm_weight_gcn_split(const float *w, int32_t nout, int32_t dn, ui
         uint16_t *d = out + ts * 3 * 512 + l * 8 + j;
         split3((o < nout && c < dn) ? w[(int64_t)o * dn + c] : 0.f, d[0], d[512], d[1024]);
     }
+}
+
+// lin_event's split pack (EncW::ev3) of a row-major W[nout][kev] on the host, with the pack launch's own index and
+// split code; returns its size in bf16 (out == NULL: the size alone)
+extern "C" int64_t tm_weight_lin_split(const float *w, int32_t nout, int32_t kev, uint16_t *out) {
+    const int nt = tmk::r16(nout) / 16;
+    const tmk::Ev3Lay L((kev + 31) / 32, tmk::ev3_tail(kev));
+    if (!out) return (int64_t)nt * L.tile();
+    for (int64_t e = 0; e < (int64_t)nt * L.elems(); ++e) {
+        int o, c, ps;
+        int64_t d0;
+        tmk::ev3_elem(L, e, o, c, d0, ps);
+        uint16_t *d = out + d0;
+        split3((o < nout && c < kev) ? w[(int64_t)o * kev + c] : 0.f, d[0], d[ps], d[2 * ps]);
+    }
+    return (int64_t)nt * L.tile();
 }
 
 extern "C" int tm_weights_set_node_zero(tm_weights *w, int32_t node_zero) {

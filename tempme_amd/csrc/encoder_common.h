@@ -28,10 +28,13 @@ struct EncW {
     // relative to itself, so those steps are the constant cos(phase) (walk_kernel's slot pass)
     const float *evc;
     int qt;   // in the walk kernel's 32-wide K steps: (de + 3 + 31) / 32
-    // lin_event's weights for the walk kernel's bf16 MFMA form (split3): per (output tile t, K step s of 32,
-    // part hi / mid / lo) one 1 KB fragment in v_mfma_f32_16x16x32_bf16's A-operand lane order -- lane l holds
-    // row 16t + (l & 15), k = 32s + 8(l >> 4) + 0..7 -- at float4 offset ((t * ns3 + s) * 3 + part) * 64;
-    // rows >= dn and k >= kev are zero.  In tm_weights::buf, so one buffer resource reaches it.
+    // lin_event's weights for the walk kernel's bf16 MFMA form (split3), tile-major: per (output tile t, K step s,
+    // part hi / mid / lo) one fragment, the steps of a tile and the parts of a step one after the other
+    // (Ev3Lay: its sizes and offsets).  ns3 = ceil(kev / 32) steps.  A 32-wide step's fragment is 1 KB in
+    // v_mfma_f32_16x16x32_bf16's A-operand lane order: lane l holds row 16t + (l & 15), k = 32s + 8(l >> 4) + 0..7.
+    // When 1 <= kev mod 32 <= 16 the last step is 16 deep instead (ev3_tail), its fragments 512 B in
+    // v_mfma_f32_16x16x16_bf16's A-operand lane order: lane l holds row 16t + (l & 15), k = 32s + 4(l >> 4) + 0..3.
+    // Rows >= dn and k >= kev are zero.  In tm_weights::buf, so one buffer resource reaches it.
     const float4 *ev3;
     int ns3;
     // event_gcn's first layer (g1) for the zero-node walk kernel's bf16 MFMA form, split3 like ev3: per (output
@@ -164,10 +167,35 @@ __host__ __device__ inline void split3(float v, uint16_t &hi, uint16_t &mid, uin
 // input feature in K slot (lane group g, element j) of pair step u of the g1 split pack (EncW::g13): elements 0..3
 // from input tile 2u, 4..7 from tile 2u + 1, each lane's 4 rows of the f32 D-tile layout
 __host__ __device__ constexpr int gcn_split_col(int u, int g, int j) { return 16 * (2 * u + (j >> 2)) + 4 * g + (j & 3); }
-// column of element (K step s, lane group g, element j) of a split pack: mode 1 = ev3 (plain 32-wide steps),
-// mode 2 = g13 (pair steps)
-__host__ __device__ constexpr int split_pack_col(int mode, int s, int g, int j) {
-    return mode == 2 ? gcn_split_col(s, g, j) : 32 * s + 8 * g + j;
+// column of element (K step s, lane group g, element j) of a split pack: mode 1 = ev3 (plain 32-wide steps; deep16:
+// its 16-deep last step, 4 elements per lane), mode 2 = g13 (pair steps)
+__host__ __device__ constexpr int split_pack_col(int mode, int s, int g, int j, bool deep16 = false) {
+    return mode == 2 ? gcn_split_col(s, g, j) : deep16 ? 32 * s + 4 * g + j : 32 * s + 8 * g + j;
+}
+// EncW::ev3 ends in a 16-deep step when the last 32-wide step would hold at most 16 real features
+__host__ __device__ constexpr bool ev3_tail(int kev) { return ((kev - 1) & 31) < 16; }
+// EncW::ev3 in bf16 units: a tile's nf 32-wide steps (3 x 512 each), then its 16-deep step (3 x 256) if it has one
+struct Ev3Lay {
+    int nf, tail;   // 32-wide steps; 1: a 16-deep step follows them
+    __host__ __device__ constexpr Ev3Lay(int ns3, bool t) : nf(ns3 - (t ? 1 : 0)), tail(t ? 1 : 0) {}
+    __host__ __device__ constexpr int tile() const { return nf * 1536 + tail * 768; }   // bf16 per output tile
+    __host__ __device__ constexpr int elems() const { return nf * 512 + tail * 256; }   // weights per output tile
+    // fragment (tile t, step s, part) -> its first bf16 (s == nf: the 16-deep step)
+    __host__ __device__ constexpr int frag(int t, int s, int part) const {
+        return t * tile() + (s < nf ? (s * 3 + part) * 512 : nf * 1536 + part * 256);
+    }
+};
+// weight e of the pack's tile-major enumeration (e < tiles * elems()) -> its row o and column c in W and its hi
+// part's bf16 index d; the mid and lo parts follow at d + ps and d + 2 ps
+__host__ __device__ inline void ev3_elem(const Ev3Lay &L, int64_t e, int &o, int &c, int64_t &d, int &ps) {
+    const int t = (int)(e / L.elems()), r = (int)(e % L.elems());
+    const bool deep16 = r >= L.nf * 512;
+    const int s = deep16 ? L.nf : r >> 9, q = deep16 ? r - L.nf * 512 : r & 511;
+    const int l = deep16 ? q >> 2 : q >> 3, j = deep16 ? q & 3 : q & 7;
+    o = 16 * t + (l & 15);
+    c = split_pack_col(1, s, l >> 4, j, deep16);
+    ps = deep16 ? 256 : 512;
+    d = (int64_t)L.frag(t, s, 0) + q;
 }
 
 // The dependency gate's logit d3 . G2 over its h2 = h/2 features in ONE fixed order, shared by the

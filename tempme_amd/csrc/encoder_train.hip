@@ -35,7 +35,7 @@ struct PackJob {
     const float *src;
     float *dst;
     int32_t so, sc, nout, k, nt, nq;
-    // 1: the three-way bf16 split pack of EncW::ev3 (nq = its 32-wide K steps; dst in bf16 units); 2: that of
+    // 1: the three-way bf16 split pack of EncW::ev3 (nq = its K steps ns3, k = kev; dst in bf16 units); 2: that of
     // EncW::g13 (nq = its pair steps, columns permuted by gcn_split_col)
     int32_t split;
     int64_t begin;
@@ -57,10 +57,22 @@ __global__ void pack_jobs_kernel(PackJobs J) {
             p.dst[e] = e < p.nout ? p.src[e] : 0.f;
             continue;
         }
-        if (p.split) {   // element (t, s, lane, j) -> its hi / mid / lo fragments (512 bf16 each)
+        if (p.split == 1) {   // weight e of EncW::ev3's enumeration -> its hi / mid / lo fragments (Ev3Lay)
+            int o, c, ps;
+            int64_t d0;
+            ev3_elem(Ev3Lay(p.nq, ev3_tail(p.k)), e, o, c, d0, ps);
+            uint16_t hi, mid, lo;
+            split3((o < p.nout && c < p.k) ? p.src[(int64_t)o * p.so + (int64_t)c * p.sc] : 0.f, hi, mid, lo);
+            uint16_t *d = reinterpret_cast<uint16_t *>(p.dst) + d0;
+            d[0] = hi;
+            d[ps] = mid;
+            d[2 * ps] = lo;
+            continue;
+        }
+        if (p.split == 2) {   // element (t, u, lane, j) of EncW::g13 -> its hi / mid / lo fragments (512 bf16 each)
             const int j = e & 7, l = (e >> 3) & 63;
             const int64_t ts = e >> 9;
-            const int o = 16 * (int)(ts / p.nq) + (l & 15), c = split_pack_col(p.split, (int)(ts % p.nq), l >> 4, j);
+            const int o = 16 * (int)(ts / p.nq) + (l & 15), c = gcn_split_col((int)(ts % p.nq), l >> 4, j);
             uint16_t hi, mid, lo;
             split3((o < p.nout && c < p.k) ? p.src[(int64_t)o * p.so + (int64_t)c * p.sc] : 0.f, hi, mid, lo);
             uint16_t *d = reinterpret_cast<uint16_t *>(p.dst) + ts * 3 * 512 + l * 8 + j;
@@ -1652,7 +1664,7 @@ void pack_all_weights(tm_weights *w, const float *const *t, hipStream_t s) {
         p.nq = w->P.ns3;
         p.split = 1;
         p.begin = total;
-        total += (int64_t)p.nt * p.nq * 512;
+        total += (int64_t)p.nt * Ev3Lay(p.nq, ev3_tail(kev)).elems();
     }
     {   // event_gcn's first layer's split pack for the zero-node walk kernel (EncW::g13), from g1's raw tensor
         PackJob &p = P.j[P.n++];

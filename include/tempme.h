@@ -740,6 +740,20 @@ int tm_tgat_attn_train_bwd(const tm_tgat_attn *a, const uint8_t *keep, float kee
                            void *workspace, void *stream);
 int64_t tm_tgat_attn_train_workspace_bytes(int64_t rows, int32_t d_time);
 
+/* The attention probabilities of one descriptor, which the forwards above keep to themselves (they store z and the
+ * softmax's max and sum): the reference's attention modules return them to their callers, and they are the
+ * attention baseline an explanation is compared against.  For row r, head h and neighbour j
+ *     probs[r,h,j] = softmax_j(s),  s_j as in the forward (same bits), masked slots at -1e10
+ *     mean[r,j]    = (probs[r,0,j] + ... + probs[r,n_head-1,j]) / n_head       (fp32, added in head order)
+ * probs [rows, n_head, n_ngh] and mean [rows, n_ngh]; either may be NULL, not both (TM_E_ARG).  a->ew is ignored:
+ * the forward multiplies by it after the softmax without renormalising.  A fully masked (row, head) is uniform,
+ * 1 / n_ngh.  No atomics: two launches give the same bits.  Out-of-range node / edge ids set *err_flag and read
+ * row 0, as in the forward.
+ * Limits (TM_E_UNSUPPORTED): d_key <= 576, n_head <= 4 (both flavours), and n_ngh <= 4096 (a row's scores,
+ * [n_ngh][4] floats, stay within 64 KiB of LDS).  rows == 0 returns TM_OK without a launch. */
+int tm_tgn_attn_probs(const tm_tgn_attn *a, float *probs, float *mean, void *stream);
+int tm_tgat_attn_probs(const tm_tgat_attn *a, float *probs, float *mean, void *stream);
+
 /* The layer tail after the attention (AttnModel :383-385, MultiHeadAttention :133-135, MergeLayer :24-34)
  * for `rows` source rows, fused, on fp32 MFMA:
  *     u   = z G^T + fc_b + query                z [rows, n_head*d_key], G = fc W_v [d_key, n_head*d_key]

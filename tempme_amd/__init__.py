@@ -10,6 +10,7 @@ Everything computes in libtempme_hip.so (hand-written gfx950 HIP kernels behind 
 include/tempme.h); importing works without a GPU, calling does not.
 """
 from ._lib import SIDE_BGD, SIDE_NONE, SIDE_SRC, SIDE_TGT, SPLIT_NULL, SPLIT_TEST, SPLIT_TRAIN, lib  # noqa: F401
+from .baselines import baseline_explanation  # noqa: F401
 from .batch_loader import RandEdgeSampler  # noqa: F401
 from .explainer import TempME, compute_node_degrees  # noqa: F401
 from .graph import NeighborFinder, adjacency_from_edges  # noqa: F401

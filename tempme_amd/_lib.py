@@ -43,7 +43,7 @@ EXPORTS = (
     "tm_encoder_pool_train_workspace_bytes", "tm_encoder_pool_train_fwd", "tm_encoder_pool_bwd", "tm_encoder_pool_wgrad",
     "tm_encoder_fwd", "tm_encoder_fwd_tab", "tm_encoder_train_supported", "tm_encoder_train_fwd", "tm_encoder_bwd", "tm_encoder_wgrad", "tm_wgrad",
     "tm_explain_train_fwd", "tm_explain_train_fwd_pad", "tm_explain_train_bwd", "tm_kl_loss", "tm_edge_importance", "tm_edge_gate_table",
-    "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_tgn_attn_train_fwd", "tm_tgn_attn_train_bwd", "tm_tgn_attn_train_workspace_bytes", "tm_tgn_attn_train_dtab", "tm_tgn_rows_reduce", "tm_tgat_attn_fwd", "tm_tgat_attn_bwd", "tm_tgat_merge_fwd", "tm_tgat_attn_train_workspace_bytes", "tm_tgat_attn_train_fwd", "tm_tgat_attn_train_bwd", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_gm_train_ok", "tm_gm_train_workspace_bytes", "tm_gm_train_fwd", "tm_gm_train_bwd", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
+    "tm_edge_table_cols", "tm_edge_tables", "tm_edge_feature_table", "tm_edge_importance_tab", "tm_tgn_attn_fwd", "tm_tgn_attn_bwd", "tm_tgn_attn_train_fwd", "tm_tgn_attn_train_bwd", "tm_tgn_attn_train_workspace_bytes", "tm_tgn_attn_train_dtab", "tm_tgn_rows_reduce", "tm_tgat_attn_fwd", "tm_tgat_attn_bwd", "tm_tgat_merge_fwd", "tm_tgat_attn_train_workspace_bytes", "tm_tgat_attn_train_fwd", "tm_tgat_attn_train_bwd", "tm_tgn_attn_probs", "tm_tgat_attn_probs", "tm_gm_packed_floats", "tm_gm_pack", "tm_gm_embed", "tm_gm_embed_bwd_ok", "tm_gm_embed_bwd", "tm_gm_packed_a_floats", "tm_gm_pack_a", "tm_gm_fused_ok", "tm_gm_train_ok", "tm_gm_train_workspace_bytes", "tm_gm_train_fwd", "tm_gm_train_bwd", "tm_dropin_create", "tm_dropin_free", "tm_dropin_forward", "tm_dropin_set_stream", "tm_dropin_gate_cache", "tm_dropin_gate_cache_clear", "tm_edge_importance_gf", "tm_edge_importance_gf3", "tm_edge_importance_gf3_bern",
     "tm_mask_least_important", "tm_rank_metrics", "tm_ranked_edges", "tm_ranked_motifs", "tm_motif_mask", "tm_profile_enable", "tm_profile_sync", "tm_profile_entry",
     "tm_beta_params", "tm_beta_rsample_bwd", "tm_adam_step", "tm_adam_step_gated", "tm_copy_many", "tm_host_register", "tm_host_unregister",
     "tm_stage_cast",
@@ -243,7 +243,9 @@ def _sig(L):
     L.tm_tgat_attn_train_workspace_bytes.argtypes = [i64, i32]
     L.tm_tgat_attn_train_fwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp]
     L.tm_tgat_attn_train_bwd.argtypes = [C.POINTER(Attn), vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.tm_mask_least_important.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
+    L.tm_tgn_attn_probs.argtypes = [C.POINTER(Attn), vp, vp, vp]
+    L.tm_tgat_attn_probs.argtypes = [C.POINTER(Attn), vp, vp, vp]
+    L.tm_mask_least_important.argtypes =[vp, i32, i32, vp, i32, vp, vp, vp]
     L.tm_rank_metrics.argtypes = [vp, i64, vp, i64, i32, i32, vp, vp]
     L.tm_ranked_edges.argtypes = [vp] * 6 + [i32, i32, i32, vp, i32, i32, i32] + [vp] * 7
     L.tm_ranked_motifs.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, i32] + [vp] * 11

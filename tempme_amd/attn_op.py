@@ -55,6 +55,24 @@ def describe(spec, qf, ngh_dense, ew):
     return a
 
 
+def attn_probs(spec, qf, ngh_dense, probs=True, mean=True):
+    """(probs [rows, n_head, n_ngh], mean [rows, n_ngh]) of one launch of tm_*_attn_probs on the descriptor a
+    forward of ``spec`` runs on: the softmax the forward keeps to itself and its mean over the heads (None for the
+    one not asked for).  No gradient; explanation weights do not enter (the forward applies them after the
+    softmax)."""
+    if not (probs or mean):
+        raise ValueError("attn_probs: ask for probs, mean or both")
+    dev = qf.device
+    R, H, N = spec["rows"], spec["n_head"], spec["n_ngh"]
+    desc = describe(spec, qf.detach(), None if ngh_dense is None else ngh_dense.detach(), None)
+    p = torch.empty((R, H, N), dtype=torch.float32, device=dev) if probs else None
+    m = torch.empty((R, N), dtype=torch.float32, device=dev) if mean else None
+    if R:
+        L.check(_entry(spec, "probs")(L.C.byref(desc), L.ptr(p), L.ptr(m), L.stream_ptr(dev)),
+                f"{_FLAVOURS[spec['flavour']]['label']} attention probabilities")
+    return p, m
+
+
 class AttnFn(torch.autograd.Function):
     """z = tm_*_attn_fwd(...) of the frozen base model; backward through tm_*_attn_bwd: the explanation weights,
     the dense neighbour table (the upper layer's input) and, for TGAT, the folded query."""
@@ -154,4 +172,4 @@ class TrainAttnFn(torch.autograd.Function):
         return d_qf, d_node, d_tab, d_time[0], d_time[1], None, None, None
 
 
-__all__ = ["AttnFn", "TrainAttnFn", "describe", "as_dev"]
+__all__ = ["AttnFn", "TrainAttnFn", "attn_probs", "describe", "as_dev"]

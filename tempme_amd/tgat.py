@@ -50,7 +50,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import attn_layer as AL
-from .attn_op import AttnFn, TrainAttnFn
+from .attn_op import AttnFn, TrainAttnFn, attn_probs
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -269,15 +269,19 @@ class TGAT(AL.HipTraining, nn.Module):
         query = torch.cat([src, src.new_zeros((R, self.e_feat_dim)), src_t], dim=1)      # [R, dk]
         return query, (query @ lw["Pt"]).contiguous()                                    # [R, H*dk]
 
-    def _attn_pass(self, pk, mi, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, ew, seg, q=None):
+    def _attn_pass(self, pk, mi, src, src_t, R, N, node_idx, ngh_dense, edge_idx, dt, mask_node, ew, seg, q=None,
+                   tap=None):
         """One AttnModel.forward (TGAT.py:362-386) over R source rows -> [R, feat]; ``q``: ``_query``'s pair
-        for these rows when it is already built."""
+        for these rows when it is already built.  ``tap`` (a list, ``attention_weights``): the pass's attention
+        probabilities and their head mean are appended to it, from one more launch on the forward's descriptor."""
         lw = pk["models"][mi]
         H, dk, fd = lw["H"], lw["dk"], self.feat_dim
         query, qf = q if q is not None else self._query(lw, src, src_t, R)
         spec = AL.attn_spec("tgat", R, N, H, dk, fd, self.time_dim, lw["temperature"], self.head_major_rows, seg,
                             node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"], edge_idx=edge_idx, dt=dt,
                             time_w=pk["freq"], time_b=pk["phase"], mask_node=mask_node, err=pk["err"])
+        if tap is not None:
+            tap.append(attn_probs(spec, qf, ngh_dense))
         z = AttnFn.apply(qf, ngh_dense, ew, spec)
         if self.fused_tail and not (torch.is_grad_enabled() and (z.requires_grad or query.requires_grad)):
             return merge_fwd(z, query, lw, fd)
@@ -304,8 +308,9 @@ class TGAT(AL.HipTraining, nn.Module):
         tensors on the device in the kernels' dtypes and the two time offsets (a dict)."""
         return AL.prep_inputs(self._dev(), nodes, eids, times, cut_time, n_segments)
 
-    def _embed(self, x, explain_weights=None):
-        """The three passes of node_embeddings on ``_prep_inputs``' dict ``x``."""
+    def _embed(self, x, explain_weights=None, tap=None):
+        """The three passes of node_embeddings on ``_prep_inputs``' dict ``x``.  ``tap``: ``_attn_pass``'s, filled by
+        pass 2 and then pass 3 (the frozen model only: ``attention_weights`` runs under no_grad)."""
         train = explain_weights is None and self._train_hip_ok()
         self._check_mode(explain_weights)
         R, N, seg = x["R"], x["N"], x["seg"]
@@ -333,8 +338,8 @@ class TGAT(AL.HipTraining, nn.Module):
             if cache is not None:
                 cache["pack"], cache["q"] = pk, (q0, q1)
         h0 = self._attn_pass(pk, 0, None, None, R, N, n1, None, e1, dt1, n1, ew1, seg, q0)
-        h1 = self._attn_pass(pk, 0, None, None, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N, q1)
-        return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg)
+        h1 = self._attn_pass(pk, 0, None, None, R * N, N, n2, None, e2, dt2, n2, ew2, seg * N, q1, tap)
+        return self._attn_pass(pk, 1, h0, t_root, R, N, None, h1.contiguous(), e1, dt1, n1, ew1, seg, None, tap)
 
     # -------------------------------------------------------------- HIP training path (tm_tgat_attn_train_*)
     def keep_mask_shapes(self, R, N):
@@ -415,6 +420,25 @@ class TGAT(AL.HipTraining, nn.Module):
     # -------------------------------------------------------------- reference API
     def affinity(self, x1, x2):
         return AL.affinity(self._pack(), x1, x2)
+
+    def attention_weights(self, src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, subgraph_src, subgraph_tgt, subgraph_bgd,
+                          prepared=None, head_mean=False):
+        """The attention probabilities of the contrast without explanation weights, as the reference's attention
+        modules return them: (hop-1 [3B, H, N], hop-2 [3B N, H, N]) fp32 device tensors, rows in the order src, tgt,
+        bgd.  Hop-1 is the third pass, the roots over the hop-1 embeddings (attn_model_list[1]); hop-2 is the second
+        pass, the hop-1 nodes over their hop-2 neighbours.  The frozen embedding pass runs once (the hop-1 keys are the
+        first layer's output) with one ``tm_tgat_attn_probs`` launch on the descriptor of each of the two passes.  A
+        padded slot carries whatever the softmax gives it (a fully padded row is uniform);
+        ``baselines.attention_explanation`` zeroes them.  ``head_mean``: the means over the heads instead,
+        (hop-1 [3B, N], hop-2 [3B N, N]).  ``prepared``: prepare_contrast's output for these inputs.  No gradient;
+        in train() mode with drop_out > 0 it raises like every frozen call."""
+        with torch.no_grad():
+            x = prepared if prepared is not None else self.prepare_contrast(
+                src_idx_l, tgt_idx_l, bgd_idx_l, cut_time_l, subgraph_src, subgraph_tgt, subgraph_bgd)
+            tap = []
+            self._embed(x, tap=tap)
+        (p2, m2), (p1, m1) = tap
+        return (m1, m2) if head_mean else (p1, p2)
 
     def _score3(self, emb, live):
         """(pos, neg) scores from the [3B, feat] embeddings of the segments src, tgt, bgd: [tgt; bgd] is emb's

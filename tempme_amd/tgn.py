@@ -51,7 +51,7 @@ import torch.nn.functional as F
 from . import _lib as L
 from . import attn_layer as AL
 from .attn_layer import cat_rows as _cat_rows  # noqa: F401  (the name it had here: tests/test_tgn_cat_rows.py)
-from .attn_op import AttnFn, TrainAttnFn, as_dev
+from .attn_op import AttnFn, TrainAttnFn, as_dev, attn_probs
 
 
 # ------------------------------------------------------------------ modules (parameter layout)
@@ -705,11 +705,12 @@ class TGN(AL.HipTraining, nn.Module):
 
     # -------------------------------------------------------------- forward pieces
     def _layer(self, pk, li, src_feat, R, N, node_idx, ngh_dense, edge_idx, edge_dense, dt, mask_node, ew, seg=0,
-               cache=None):
+               cache=None, tap=None):
         """One TemporalAttentionLayer over R source rows (embedding_module.py:181-216).  ``cache`` (the
         prepared inputs' dict): the query and its folded projection depend on the source rows and the frozen
         weights only, so the training step's two contrasts of one batch (temp_exp_main.py:597, :611) compute
-        them once."""
+        them once.  ``tap`` (a list, ``attention_weights``): the layer's attention probabilities and their head
+        mean are appended to it, from one more launch on the forward's descriptor."""
         lw = pk["layers"][li]
         H, dk = lw["H"], lw["dk"]
         dn = self.n_node_features
@@ -727,20 +728,26 @@ class TGN(AL.HipTraining, nn.Module):
                             node_tab=pk["tab"], node_idx=node_idx, edge_tab=pk["etab"], edge_idx=edge_idx,
                             edge_dense=edge_dense, dt=dt, time_w=pk["tw"], time_b=pk["tb"], mask_node=mask_node,
                             err=pk["err"])
+        if tap is not None:
+            tap.append(attn_probs(spec, qf, ngh_dense))
         z = AttnFn.apply(qf, ngh_dense, ew, spec)
         h = AL.mha_tail(z, query, lw["G"].t(), lw["fcb"], lw["lnw"], lw["lnb"])
         x = torch.cat([h, src_feat], dim=1)
         return F.linear(F.relu(F.linear(x, lw["m1w"], lw["m1b"])), lw["m2w"], lw["m2b"])
 
     def node_embeddings(self, nodes, eids, times, cut_time, explain_weights=None, edge_attr=None, n_segments=1,
-                        prepared=None):
+                        prepared=None, tap=None):
         """embedding_update(_attr) + embedding_update_layer (embedding_module.py:314-393) for
         nodes = [n0 [R1], n1 [R1,N], n2 [R1,N^2]], eids/times = [hop1, hop2] -> [R1, d].
         n_segments > 1 stacks independent contrast batches (R1 = n_segments * 3B rows): every row
         gives the same result as in its own call (the head-major pairing stays inside its batch).
         ``prepared``: the output of ``_prep_inputs`` for these inputs (built once when the same
-        subgraphs go through several contrasts, as the training step's two do)."""
+        subgraphs go through several contrasts, as the training step's two do).  ``tap``: ``_layer``'s, filled
+        with layer 0's pair and then layer 1's (the frozen model only)."""
         if self._stateful():
+            if tap is not None:
+                raise NotImplementedError("TGN attention weights with memory updates (forbidden_memory_update="
+                                          "False): the frozen model's layers are tapped, as the explainer reads it")
             x = prepared if prepared is not None else self._prep_inputs(nodes, eids, times, cut_time, edge_attr,
                                                                         n_segments)
             # no events here: the embeddings over the updated memory, the state left as it is
@@ -757,10 +764,10 @@ class TGN(AL.HipTraining, nn.Module):
         # layer 0 (attention_models[0]): hop-1 nodes attend over their hop-2 neighbours
         cache = x if prepared is not None else None
         y0 = self._layer(pk, 0, lambda: tab[x["n1l"]], R1 * N, N, x["n2"], None, x["e2"], x["ed2"], x["dt2"],
-                         x["n2"], ew2, seg1 * N, cache)
+                         x["n2"], ew2, seg1 * N, cache, tap)
         # layer 1 (attention_models[1]): roots attend over the hop-1 embeddings
         y1 = self._layer(pk, 1, lambda: tab[x["n0"]], R1, N, None, y0.contiguous(), x["e1"], x["ed1"], x["dt1"],
-                         x["n1"], ew1, seg1, cache)
+                         x["n1"], ew1, seg1, cache, tap)
         return y1
 
     def _prep_inputs(self, nodes, eids, times, cut_time, edge_attr=None, n_segments=1):
@@ -798,6 +805,29 @@ class TGN(AL.HipTraining, nn.Module):
 
     def affinity(self, x1, x2):
         return AL.affinity(self._pack(), x1, x2)
+
+    def attention_weights(self, src_idx, tgt_idx, bgd_idx, cut_time, subgraph_src, subgraph_tgt, subgraph_bgd,
+                          prepared=None, head_mean=False):
+        """The attention probabilities of the contrast without explanation weights, as the reference's attention
+        modules return them: (hop-1 [3B, H, N], hop-2 [3B N, H, N]) fp32 device tensors, rows in the order src, tgt,
+        bgd.  Hop-1 is layer 1, the roots over the hop-1 embeddings; hop-2 is layer 0, the hop-1 nodes over their
+        hop-2 neighbours.  The frozen embedding pass runs once (the hop-1 keys are layer 0's output) with one
+        ``tm_tgn_attn_probs`` launch per layer on the forward's descriptor.  A padded slot carries whatever the
+        softmax gives it (a fully padded row is uniform); ``baselines.attention_explanation`` zeroes them.
+        ``head_mean``: the means over the heads instead, (hop-1 [3B, N], hop-2 [3B N, N]).  ``prepared``:
+        prepare_contrast's output for these inputs.  No gradient.  A stateful TGN (forbidden_memory_update=False)
+        raises NotImplementedError: the explainer reads the frozen model."""
+        if self._stateful():
+            raise NotImplementedError("TGN.attention_weights with memory updates (forbidden_memory_update=False): "
+                                      "the frozen model's layers are tapped, as the explainer reads it")
+        with torch.no_grad():
+            if prepared is None:
+                prepared = self.prepare_contrast(src_idx, tgt_idx, bgd_idx, cut_time, subgraph_src, subgraph_tgt,
+                                                 subgraph_bgd)
+            tap = []
+            self.node_embeddings(None, None, None, None, prepared=prepared, tap=tap)
+        (p2, m2), (p1, m1) = tap
+        return (m1, m2) if head_mean else (p1, p2)
 
     def contrast(self, src_idx, tgt_idx, bgd_idx, cut_time, e_idx, subgraph_src, subgraph_tgt, subgraph_bgd,
                  explain_weights=None, edge_attr=None, prepared=None):
